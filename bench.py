@@ -17,6 +17,11 @@ torch.distributed.run (WORLD_SIZE set) the process is one rank.
 Grays/s = (closest-hit + shadow rays traced, all ranks) / wall time of the K timed frames
 (barrier + device sync on both sides, max over ranks).  Inputs (scene, BVH, random offsets)
 are resident in HBM before the timed region.
+
+A plain run does what that figure needs: set-up, warm-up, the timed steps, --dump-outputs, the
+JSON line.  `--full` adds the measurements that take runs of their own (rocprofv3 PMC passes, the
+counting frame, the kernels-alone frames and the roofline built on them, the CPU baseline); in a
+plain line `roofline`, `cpu_baseline`, `ms_per_frame` and `config.visits_per_ray` are null.
 """
 import argparse
 import importlib
@@ -290,9 +295,37 @@ def parse(argv=None):
                         "through host memory; ranks may share a GPU, which RCCL refuses)")
     p.add_argument("--dump-radiance", default=None,
                    help="rank 0 writes the newest frame's radiance (H, W, 4) float32 here (.npy) after the timed region")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32): radiance (H, W, 4) "
+                        "and, on one GPU, depth (H, W) and motion (H, W, 2); above 64 MB in all, the same fixed seeded "
+                        "sample of pixels of each (rows of the flattened image, ascending pixel index)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the rocprofv3 PMC passes, the counting frame, the "
+                        "kernels-alone frames and the roofline built on them, the CPU baseline (each still has its "
+                        "--no-* switch); without it the run sets up, warms up, times the steps and prints the line")
     p.add_argument("--dry-run", action="store_true",
                    help="launcher / collective test on the CPU: gloo instead of RCCL, a stub frame instead of the renderer")
     return p.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each (H, W, ...) image of `arrays` as path/<name>.npy, float32.  Up to
+    DUMP_LIMIT_BYTES in all they are written whole; above it every image is written as the same
+    sample of pixels, (K, channels) rows in ascending pixel index y * W + x, drawn with a fixed seed
+    (the same pixels in every run of the same frame size)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    h, w = next(iter(arrays.values())).shape[:2]
+    per_pixel = sum(v.nbytes for v in arrays.values()) // (h * w)
+    keep = (DUMP_LIMIT_BYTES - 1024 * len(arrays)) // per_pixel   # room for the .npy headers
+    idx = None
+    if keep < h * w:
+        idx = np.sort(np.random.default_rng(20240607).choice(h * w, size=keep, replace=False))
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v if idx is None else v.reshape(h * w, -1)[idx])
 
 
 # ---- launcher -----------------------------------------------------------------------------------
@@ -369,7 +402,7 @@ def main():
     # PMC passes (one GPU, before this process touches the GPU): HBM bytes and L2 hit rates per
     # kernel, measured on the same workload with the kernels alone
     pmc, pmc_csvs, pmc_err = None, {}, None
-    if not a.no_pmc and not a.dry_run and max(world_env, 1) == 1 and a.pipeline == "wavefront":
+    if a.full and not a.no_pmc and not a.dry_run and max(world_env, 1) == 1 and a.pipeline == "wavefront":
         pmc, pmc_csvs, pmc_err = run_pmc(a)
     import torch
     import torch.distributed as dist
@@ -493,14 +526,16 @@ def main():
             if ev is not None:
                 gather_events.append(ev)
 
-    # counting frame (untimed): node visits / triangle tests per ray for the roofline numerator
-    R.set_counting(True)
-    R.frameIndex = 0
-    R.draw(tiles=tiles)
-    R.wait()
-    cst = R.stats()
-    R.set_counting(False)
-    R.samplesPerPixel = a.spp  # resets frameIndex (didSet)
+    # counting frame (untimed, --full): node visits / triangle tests per ray for the roofline numerator
+    cst = None
+    if a.full:
+        R.set_counting(True)
+        R.frameIndex = 0
+        R.draw(tiles=tiles)
+        R.wait()
+        cst = R.stats()
+        R.set_counting(False)
+        R.samplesPerPixel = a.spp  # resets frameIndex (didSet)
 
     for _ in range(a.warmup):
         submit()
@@ -548,6 +583,11 @@ def main():
         return
     if a.dump_radiance:
         np.save(a.dump_radiance, R.radiance())
+    if a.dump_outputs:
+        outs = {"radiance": R.radiance()}
+        if n == 1:   # multi-GPU: only the radiance is gathered
+            outs["depth"], outs["motion"], _ = R.aux()
+        dump_outputs(a.dump_outputs, outs)
 
     value = rays_all / dt / 1e9
     ms_per_step = dt / a.steps * 1e3
@@ -557,30 +597,32 @@ def main():
         cus = 256
     ranks = n if n > 1 else max(a.emulate_ranks, 1)
     pixels = a.width * a.height / ranks
-    table = kernel_table(a, cst, s0, s1, a.steps, pixels, cus)
-    if s1.frames_in_flight > 1 and not a.no_isolated:
-        # after the timed region: the same frame with one frame in flight, so every kernel has the
-        # GPU to itself; the roofline prices these launches, and their wall time per frame is the
-        # single-frame latency
-        i0, i1, ms_frame, cst_alone = isolated(R, tiles, torch, dev, a.isolated_frames)
-        alone, shared = kernel_table(a, cst_alone, i0, i1, a.isolated_frames, pixels, cus), table
-        stage_alone = (np.array(list(i1.total_kernel_ms)) - np.array(list(i0.total_kernel_ms))) / a.isolated_frames
-    elif s1.frames_in_flight == 1:
-        alone, shared, ms_frame, stage_alone = table, None, ms_per_step, None
-    else:   # --no-isolated: the shared-GPU launches, flagged
-        alone, shared, ms_frame, stage_alone = table, None, None, None
-    roof = roofline(alone, shared, pmc, pmc_err, ms_frame, ms_per_step, pmc_csvs)
-    if roof.get("shade_l2_hit") is not None:
-        roof["shade_l2_hit_kernel"] = ("wf_shade on hit-sorted input (--sort-bins)" if a.sort_bins > 0 else
-                                       "wf_shade of the default pipeline: hits shaded in queue order (rays grouped by "
-                                       "octant inside each block's appends only; no queue-wide ray or hit sort, DESIGN.md §3.5)")
-    if alone is table and s1.frames_in_flight > 1:
-        roof["not_a_kernel_measurement"] = True
+    roof, ms_frame, stage_alone = None, None, None
+    if a.full:
+        table = kernel_table(a, cst, s0, s1, a.steps, pixels, cus)
+        if s1.frames_in_flight > 1 and not a.no_isolated:
+            # after the timed region: the same frame with one frame in flight, so every kernel has the
+            # GPU to itself; the roofline prices these launches, and their wall time per frame is the
+            # single-frame latency
+            i0, i1, ms_frame, cst_alone = isolated(R, tiles, torch, dev, a.isolated_frames)
+            alone, shared = kernel_table(a, cst_alone, i0, i1, a.isolated_frames, pixels, cus), table
+            stage_alone = (np.array(list(i1.total_kernel_ms)) - np.array(list(i0.total_kernel_ms))) / a.isolated_frames
+        elif s1.frames_in_flight == 1:
+            alone, shared, ms_frame = table, None, ms_per_step
+        else:   # --no-isolated: the shared-GPU launches, flagged
+            alone, shared = table, None
+        roof = roofline(alone, shared, pmc, pmc_err, ms_frame, ms_per_step, pmc_csvs)
+        if roof.get("shade_l2_hit") is not None:
+            roof["shade_l2_hit_kernel"] = ("wf_shade on hit-sorted input (--sort-bins)" if a.sort_bins > 0 else
+                                           "wf_shade of the default pipeline: hits shaded in queue order (rays grouped by "
+                                           "octant inside each block's appends only; no queue-wide ray or hit sort, DESIGN.md §3.5)")
+        if alone is table and s1.frames_in_flight > 1:
+            roof["not_a_kernel_measurement"] = True
     stage_ms = (np.array(list(s1.total_kernel_ms)) - np.array(list(s0.total_kernel_ms))) / a.steps
     graphs = {k: int(d("total_graph_" + k)) for k in ("replays", "captures", "fallbacks", "eager")}
 
     cpu = None
-    if not a.no_cpu and n == 1:
+    if a.full and not a.no_cpu and n == 1:
         cpu = cpu_baseline(rt, scene, R, a)
 
     line = {
@@ -593,6 +635,7 @@ def main():
         "dist_backend": dist.get_backend() if n > 1 else None,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": round(ms_per_step, 3),
         # single-frame latency: one frame in flight, wall time per frame (the metric's ms/frame);
         # ms_per_step is the throughput interval with frames in flight
@@ -623,7 +666,8 @@ def main():
             # captured HIP graphs, fresh captures, refused captures (eager), eager by choice
             # the counting frame's BVH work per traced ray (closest-hit + shadow)
             "visits_per_ray": {"nodes": round(cst.node_visits / max(cst.closest_rays + cst.shadow_rays, 1), 3),
-                               "tris": round(cst.tri_tests / max(cst.closest_rays + cst.shadow_rays, 1), 3)},
+                               "tris": round(cst.tri_tests / max(cst.closest_rays + cst.shadow_rays, 1), 3)}
+            if cst is not None else None,
             "graphs": graphs,
             "move": {"dx": a.move, "mode": a.move_mode, "auto_rebuilds": int(s1.total_auto_rebuilds),
                      "bvh_cost_built": round(float(s1.bvh_cost_built), 2),

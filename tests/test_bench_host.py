@@ -57,3 +57,28 @@ def test_pmc_child_args_keep_the_workload():
     for k, v in (("--scene", "c2"), ("--width", "1280"), ("--height", "720"), ("--bounces", "4"),
                  ("--emulate-ranks", "8")):
         assert args[args.index(k) + 1] == v
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files; whole images up to the byte limit, above it the same seeded
+    pixel sample of every image (ascending pixel index), identical from call to call."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    rad, depth = rng.random((9, 7, 4)), rng.random((9, 7)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"radiance": rad, "depth": depth})
+    a = np.load(tmp_path / "a" / "radiance.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, rad.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "depth.npy"), depth)
+    # 20 bytes a pixel: room for 30 of the 63 pixels
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 30 * 20 + 2 * 1024)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"radiance": rad, "depth": depth})
+    b, bd = np.load(tmp_path / "b" / "radiance.npy"), np.load(tmp_path / "b" / "depth.npy")
+    assert b.shape == (30, 4) and bd.shape == (30, 1) and b.dtype == bd.dtype == np.float32
+    flat = depth.reshape(-1)
+    idx = [int(np.flatnonzero(flat == v)[0]) for v in bd[:, 0]]
+    assert idx == sorted(set(idx))   # distinct pixels, ascending
+    assert np.array_equal(b, rad.astype(np.float32).reshape(-1, 4)[idx])
+    assert np.array_equal(b, np.load(tmp_path / "c" / "radiance.npy"))
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= bench.DUMP_LIMIT_BYTES

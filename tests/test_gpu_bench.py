@@ -1,10 +1,12 @@
 """bench.py's contract on a small workload (the driver parses its one JSON line): required keys,
-the roofline and cpu_baseline objects, and the per-rank emulation mode."""
+the roofline and cpu_baseline objects of a --full run, the per-rank emulation mode, and the plain
+run with --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +25,7 @@ def _run(*args):
 def test_bench_line_contract():
     # 12 steps over the frame slots: each slot's first frame may capture, the later ones replay
     d = _run("--scene", "c1", "--width", "128", "--height", "96", "--spp", "2", "--bounces", "3", "--steps", "12",
-             "--warmup", "4", "--cpu-seconds", "0.5")
+             "--warmup", "4", "--cpu-seconds", "0.5", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -66,9 +68,31 @@ def _roofline_consistent(d):
 
 def test_bench_emulated_rank_and_animation():
     d = _run("--scene", "c5", "--width", "128", "--height", "96", "--spp", "1", "--bounces", "2", "--steps", "3",
-             "--warmup", "1", "--no-cpu", "--no-pmc", "--animate", "--emulate-ranks", "2")
+             "--warmup", "1", "--full", "--no-cpu", "--no-pmc", "--animate", "--emulate-ranks", "2")
     assert d["value"] > 0 and d["config"]["animate"] is True and d["cpu_baseline"] is None
     # --no-pmc: no HBM byte count, so no HBM fraction; the algorithmic rate is reported beside it
     r = d["roofline"]
     assert r["frac"] is None and r["achieved"] is None and r["traffic"] is None
     assert r["frac_source"].startswith("none") and r["frac_algorithmic"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without --full the line keeps the headline fields and leaves out what takes runs of its own;
+    --dump-outputs writes the last timed frame as float32 arrays, the radiance being the one
+    --dump-radiance writes."""
+    out = tmp_path / "outs"
+    d = _run("--scene", "c1", "--width", "100", "--height", "72", "--spp", "2", "--bounces", "3", "--steps", "5",
+             "--warmup", "2", "--dump-outputs", str(out), "--dump-radiance", str(tmp_path / "rad.npy"))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert k in d, k
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["config"]["visits_per_ray"] is None
+    g = d["config"]["graphs"]   # exactly the timed steps were submitted between the two stats reads
+    assert g["replays"] + g["captures"] + g["fallbacks"] + g["eager"] == 5
+    assert sorted(os.listdir(out)) == ["depth.npy", "motion.npy", "radiance.npy"]
+    rad, depth, motion = (np.load(out / (n + ".npy")) for n in ("radiance", "depth", "motion"))
+    assert rad.dtype == depth.dtype == motion.dtype == np.float32
+    assert rad.shape == (72, 100, 4) and depth.shape == (72, 100) and motion.shape == (72, 100, 2)
+    assert np.isfinite(rad[..., :3]).all() and rad[..., :3].max() > 0
+    assert np.array_equal(rad, np.load(tmp_path / "rad.npy"))

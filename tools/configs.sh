@@ -1,17 +1,18 @@
 #!/bin/bash
 # Every BASELINE config through bench.py at the library defaults (one GPU), the emulated per-rank
 # shares of the 2 / 4 / 8-way C3g split, and one rank of configs[3]'s 8-way 4K x 16 split
-# (bench.py --emulate-ranks N: rank 0's tiles, no gather).  Every row runs bench.py's PMC passes, so
+# (bench.py --emulate-ranks N: rank 0's tiles, no gather).  Every row runs bench.py --full with its PMC passes, so
 # its frac is an HBM fraction (rocprofv3 bytes over the launch time alone); the algorithmic rate is
 # printed in GB/s beside it (it counts L2 / MALL hits too and is no fraction of HBM).  One summary
 # line per run.
 set -o pipefail
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 export TMPDIR=/tmp
 run() {
   tag=$1; shift
-  timeout -k 10 400 python -u bench.py "$@" > gpurun_out/cfg_$tag.log 2>&1 || { tail -c 1500 gpurun_out/cfg_$tag.log; exit 1; }
-  python3 - gpurun_out/cfg_$tag.log $tag <<'PY'
+  timeout -k 10 400 python -u bench.py --full "$@" > $OUT/cfg_$tag.log 2>&1 || { tail -c 1500 $OUT/cfg_$tag.log; exit 1; }
+  python3 - $OUT/cfg_$tag.log $tag <<'PY'
 import json, sys
 d = json.loads([x for x in open(sys.argv[1]) if x.startswith("{")][-1])
 r, c = d["roofline"], d["cpu_baseline"]
