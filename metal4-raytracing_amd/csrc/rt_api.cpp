@@ -72,21 +72,6 @@ struct Geo {
 #endif
 constexpr int kMaxSlots = RT_MAX_SLOTS;
 constexpr int kGens = kMaxSlots;   // generations allocated at most (ngens of them in use)
-// default finish threshold with 2 / 3 / 4 frames in flight (C3g sweeps: 1.25M, 1M and 512K paths;
-// round 2, with the DP-collapsed tree and the lighter shading kernels, two slots: 2M 5.88 / 5.89,
-// 1.57M 5.90 (C3g enters the finish one round earlier between 1.5M and 1.57M live paths),
-// 1.5M 5.97 / 6.02, 1M 6.02 / 6.00 Grays/s; four slots serve the small frames of multi-GPU ranks:
-// 8-way split 2.92 -> 3.46 Grays/s per rank at 512K against 1M in round 1, 256K-786K within noise
-// in round 2, with the finish kernel on 20 % of the grid)
-// Final round-2 kernels, 8-way share with four slots: 256K 4.14 / 4.13, 512K 4.25 / 4.26, 768K
-// 4.32 / 4.30 Grays/s per rank -> 768K for four slots.
-constexpr int kTailInFlightTab[9] = {0, 0, 1310720, 1048576, 786432, 524288, 524288, 524288, 524288};
-constexpr int kTailInFlight(int nfl) { return kTailInFlightTab[nfl < 8 ? nfl : 8]; }
-// Default frames in flight (render_frame): their buffers, ~300 B per allocated path (pixels x (spp +
-// motion-adaptive extra samples)) and slot (128 B path state and ray slots + 176 B of queues), stay
-// within kSlotBudget of the 288 GB (1080p x 4 + 2 extra: 3.7 GB a slot; configs[3]'s 3840x2160x16
-// frame on one GPU: 40 GB a slot, two slots).
-constexpr uint64_t kSlotBudget = 96ull << 30, kSlotBytesPerPath = 300;
 constexpr int kMotionTargets = kMaxSlots + 1;
 // Default slots: eight when the HIP runtime gives the process at least eight hardware
 // queues (GPU_MAX_HW_QUEUES, read once; HIP's default is 4), so every slot's stream has a queue of
@@ -100,16 +85,6 @@ static int small_frame_slots() {
     }();
     return n;
 }
-// Frames below this many allocated paths keep at most four slots: a configs[0]-sized frame (65K
-// paths, ~0.05 ms) on eight slots / eight queues ran bimodally, 2.04-2.10 or 0.55-0.62 Grays/s
-// (3 of 6 runs slow), against 2.10-2.54 on four (round 5); the 8-way C3g share (1M paths) gains
-// 9 % from eight slots and was steady.  Round 6 traced six such runs (profiles/r06_c1_bimodal.txt):
-// the kernels take the same time in slow and fast runs, the slow ones overlap their frames less
-// (0.94-1.10 kernels at once against 1.38) -- slot streams sharing hardware queues serialise a
-// frame whose GPU work is ~0.12 ms; at four slots there is queue room to spare.
-constexpr uint64_t kSmallFramePaths = 1ull << 19;
-constexpr uint64_t kSmallShareBasePaths = 2500000;   // see rt_render_frame's tail
-constexpr int kTailShare = 786432;
 // rt_set_tuning bounds: a chunk grab past the end of a queue still adds the chunk size to its
 // 32-bit counter, once per wave (at most ~16K waves resident); 4096 x 16K stays far below 2^32
 // minus any queue the library allocates.  The shade grid is grid-stride, so more blocks than
@@ -1099,13 +1074,8 @@ rt_status rt_render_frame(rt_ctx* c, const Uniforms* U, const rt_tile_set* tiles
     const int spp = std::max(U->samplesPerPixel, 1);
     const int max_extra = U->enableMotionAdaptiveSampling ? std::max(U->motionSamplingMaxExtraSamples, 0) : 0;
     int nfl = 1;
-    if (wavefront && c->stream == c->own_stream) {
-        const uint64_t frame_paths = (uint64_t)own * ts * ts * (uint64_t)(spp + max_extra);
-        const uint64_t slots = frame_paths < kSmallFramePaths ? std::min(4, small_frame_slots()) : small_frame_slots();
-        nfl = c->max_in_flight > 0 ? c->max_in_flight
-                                   : (int)std::max<uint64_t>(2, std::min<uint64_t>(slots,
-                                                                              kSlotBudget / (frame_paths * kSlotBytesPerPath + 1)));
-    }
+    if (wavefront && c->stream == c->own_stream)
+        nfl = wf_in_flight((uint64_t)own * ts * ts * (uint64_t)(spp + max_extra), small_frame_slots(), c->max_in_flight);
     const int k = c->frame_no > 0 ? (c->last_slot + 1) % nfl : 0;
     FrameSlot& F = c->slot[k];
     const hipStream_t stream = slot_stream(c, k);
@@ -1210,16 +1180,11 @@ rt_status rt_render_frame(rt_ctx* c, const Uniforms* U, const rt_tile_set* tiles
     if (wavefront) {
         const char* err = nullptr;
         F.wfs = WfFrameStats{};
-        // finish threshold: with frames in flight the next frames' bulk rounds overlap this
-        // frame's tail, so more bulk rounds and a shorter tail pay (kTailInFlight: C3g, 2 in
-        // flight 1.25M paths against the one-frame-at-a-time optimum of 4M; 3 in flight 1M)
-        int tail = c->tail_paths ? c->tail_paths : (nfl > 1 ? kTailInFlight(nfl) : 0);
-        // eight frames in flight and a frame of at most 2.5M base paths (a multi-GPU rank's share):
-        // 768K (round 5, finish on 12 % of the grid: 8-way share 7.02 -> 7.20, 4-way 8.44 -> 8.54
-        // Grays/s; 1M hands the 8-way share's whole frame to the finish: 6.08)
-        if (!c->tail_paths && nfl >= 8 && (uint64_t)own * ts * ts * (uint64_t)spp <= kSmallShareBasePaths) tail = kTailShare;
-        if (own > 0 && !run_wavefront(S, P, F.wf, c->tuning, own, c->counting, c->spans, tail, c->sort_bins, extra_pass,
-                                      nfl, stream, cross ? prev.done : nullptr, &F.wft, &F.wfs, &err, c->graphs))
+        // finish threshold, grid shares and team drain by the frame's size and the frames in flight
+        const WfSchedule sched = wf_schedule((uint32_t)own * (uint32_t)ts * (uint32_t)ts * (uint32_t)spp, nfl,
+                                             c->tail_paths, c->tuning);
+        if (own > 0 && !run_wavefront(S, P, F.wf, c->tuning, sched, own, c->counting, c->spans, c->sort_bins, extra_pass,
+                                      stream, cross ? prev.done : nullptr, &F.wft, &F.wfs, &err, c->graphs))
             FAIL(c, RT_ERR_HIP, std::string("wavefront: ") + (err ? err : "?"));
         if (own == 0 && cross) HIPC(c, hipStreamWaitEvent(stream, prev.done, 0));
     } else {

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_wf_schedule.h"
 
 namespace rt {
 
@@ -166,28 +167,6 @@ struct WfFrameStats {
     int finish_launches;
     int graph_mode;                 // kGraph*: how the frame was submitted
 };
-// The wavefront kernels' scheduling parameters, resolved (rt_tuning in rt_api.h: 0 = default there;
-// rt_api.cpp fills these in).  Per context: the library reads no environment variable for them.
-struct WfTuning {
-    uint32_t tail = 4194304;      // finish threshold one frame at a time (frames in flight: rt_api.cpp kTailInFlight)
-    int refill_min = 8;           // a wave refills once this many of its lanes are idle
-    int chunk = 64;               // rays per chunk grab of the traversal kernel
-    int fchunk = 64;              // paths per chunk grab of the finish kernel
-    int shade_min = 24;           // the finish kernel shades once this many lanes wait
-    int shade_min_x = -50;        // the same once its queue ran out (< 0: that percentage of the wave's busy lanes)
-    int team = -1;                // finish drain lanes per query (-1: 4 for frames of kTeamAutoMin .. kTeamAutoPaths
-                                  // base paths, off otherwise; 0: off; 2 / 4 / 8)
-    int finish_frac = 0;          // percent of the resident grid the finish launch takes (0 = by frames in flight)
-    int trace_frac = 0;           // percent of the resident grid the bulk wf_trace launches take (0 = by frames in flight)
-    int log = 0;                  // 1: per-round queue sizes, stage times and finish diagnostics on stderr;
-                                  // 2: also the finish paths' segment counts (one atomic per path)
-    bool host_ctl = false;        // host-driven rounds (queue sizes read back every round)
-    unsigned shade_blocks = 2048; // wf_shade grid (grid-stride loop), a multiple of 8: 1.6 waves of the resident
-                                  // grid leaves CUs to the other frames in flight
-};
-
-// Runs one frame; returns false on a HIP error (message in *err).
-// tail_paths: finish-kernel threshold (0 = default / RT_TAIL_RAYS).
 // Host-side record of a frame enqueued with device-side control: events between the launches and
 // which stage each interval belongs to; collected once the frame is done (wavefront_collect).
 struct WfTimeline {
@@ -211,16 +190,20 @@ struct WfTimeline {
     int graph_mode = 0;          // the pending frame: kGraph* (rt_stats total_graph_*)
 };
 constexpr int kGraphEager = 0, kGraphReplay = 1, kGraphCapture = 2, kGraphFallback = 3;
-// Runs (host-driven: queue sizes read back every round; with RT_WF_LOG / RT_WF_HOST=1) or enqueues (device-driven, the default: `tl` receives the timeline, stats come
-// from wavefront_collect after the stream finished) one frame; false on a HIP error (*err).
-// sort_bins: hit-sort bins (0 = no sort).  extra_pass: the motion-adaptive extra samples can be
-// non-zero this frame (something moved in this or the previous frame); the device-driven mode
-// skips their pass otherwise.  in_flight: frames that can overlap this one (> 1: the finish
-// kernel takes 1 / in_flight of the resident grid and leaves the rest to the other frames).  prev_done (may be null): the previous frame, in flight on another
-// stream; the extra-sample pass and the resolve (which read its accumulation and motion outputs)
-// are ordered after it, everything before them overlaps it.
-bool run_wavefront(const DevScene& S, const FrameParams& P, WavefrontBuffers& W, const WfTuning& tu, int own_tiles,
-                   bool count, bool spans, int tail_paths, int sort_bins, bool extra_pass, int in_flight,
+// One wavefront frame of `own_tiles` tiles on `stream` (rt_wavefront_host.cpp); false on a HIP
+// error (*err).  Device-driven rounds, the default, enqueue the whole frame and return: `tl`
+// receives the timeline and wavefront_collect fills the stats once the stream has finished;
+// graphs: as two replayed HIP graphs.  Host-driven rounds (tu.host_ctl or tu.log set, no `tl`, or
+// a finish threshold <= 1) read the queue sizes back every round; *fs is complete on return.
+// sched: the finish threshold, grid shares and team drain (wf_schedule, rt_wf_schedule.h).
+// count: the traversal statistics counters; spans: device-clock launch spans.  sort_bins: hit-sort
+// bins (0 = no sort).  extra_pass: the motion-adaptive extra samples can be non-zero this frame
+// (something moved in this or the previous frame); device-driven rounds skip their pass otherwise.
+// prev_done (may be null): the previous frame, in flight on another stream; the extra-sample pass
+// and the resolve (which read its accumulation and motion outputs) are ordered after it,
+// everything before them overlaps it.
+bool run_wavefront(const DevScene& S, const FrameParams& P, WavefrontBuffers& W, const WfTuning& tu,
+                   const WfSchedule& sched, int own_tiles, bool count, bool spans, int sort_bins, bool extra_pass,
                    hipStream_t stream, hipEvent_t prev_done, WfTimeline* tl, WfFrameStats* fs, const char** err,
                    bool graphs = true);
 bool wavefront_collect(const WavefrontBuffers& W, WfTimeline& T, WfFrameStats* fs, const char** err);

@@ -22,21 +22,17 @@
 // Results are bit-identical to the megakernel: per-path arithmetic is the same shade_step,
 // the accumulation order per path is the reference's (emission of step s, then its shadow
 // contribution, then step s+1), and samples are summed per pixel in sample order.
+//
+// This file holds the kernels only; rt_wavefront_host.cpp launches them, through wf_kernels() below.
 #include "rt_shade.h"
+#include "rt_wavefront.h"
 
-#include <atomic>
-#include <cstdio>
-#include <cstring>
-#include <vector>
+#include <array>
+#include <utility>
 
 namespace rt {
 
 namespace {
-
-// frames of kTeamAutoMin .. kTeamAutoPaths base paths use the finish kernel's team drain by default
-// (rt_tuning.team = 0): the C3g rank shares gain, the tiny C1 frame (65K paths) loses 7.5 %
-constexpr uint32_t kTeamAutoPaths = 2500000u;
-constexpr uint32_t kTeamAutoMin = 262144u;
 
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ uint32_t mbcnt64(unsigned long long m) {
@@ -153,54 +149,10 @@ __device__ __forceinline__ uint32_t pack_state(int bounce, int tpass, int step) 
     return (uint32_t)bounce | ((uint32_t)tpass << 8) | ((uint32_t)step << 16);
 }
 
-// n / d for 32-bit n by a multiply-high and two shifts (Granlund, Montgomery, PLDI 1994, fig. 4.1):
-// the path-id -> pixel mappings run per refill / per shaded hit, where an integer division by a
-// run-time divisor costs ~30 VALU instructions
-struct FastDiv {
-    uint32_t d, m, s1, s2;
-};
-static FastDiv make_fastdiv(uint32_t d) {
-    FastDiv f;
-    f.d = d;
-    uint32_t l = 0;
-    while (l < 32 && (1ull << l) < d) ++l;
-    f.m = (uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-    f.s1 = l < 1 ? l : 1;
-    f.s2 = l > 1 ? l - 1 : 0;
-    return f;
-}
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
+__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {   // n / f.d (make_fastdiv)
     const uint32_t t = __umulhi(f.m, n);
     return (t + ((n - t) >> f.s1)) >> f.s2;
 }
-
-struct WfParams {
-    WavefrontBuffers W;
-    uint32_t base_paths;   // own pixels * spp
-    uint32_t own_pixels;
-    uint32_t seg_cap;      // entries per queue segment
-    int spp;
-    int refill_min;        // wf_trace / wf_finish_step refill once at least this many lanes of a wave are idle
-    int chunk;             // wf_trace: rays per chunk grab
-    uint32_t tail;         // live paths below which wf_finish_step runs the rest
-    uint32_t sort_bins;    // hit-sort bins (0 = shade reads the extend queue unsorted)
-    int diag;              // wf_finish_step: record the diagnostics slots (RT_WF_LOG)
-    int shade_min;         // wf_finish_step: shade once this many lanes wait (or none traverses)
-    int shade_min_x;       // wf_finish_step: the same once the launch's queue is exhausted (< 0: percent of busy lanes)
-    int team;              // wf_finish_step: lanes per query in the drain (0: no team drain)
-    int fchunk;            // wf_finish_step: paths per chunk grab
-    int finish_frac;       // percent of the resident grid the finish launch takes
-    int trace_frac;        // percent of the resident grid the bulk wf_trace launches take
-    unsigned shade_blocks; // wf_shade grid
-    int spans;             // record device-clock launch spans (rt_set_device_spans)
-    int dev_ctl;           // device-side control (enqueue_wavefront): kernels read their queue sizes from
-                           // the counters and skip once the live count fell below `tail`
-    int finish_q;          // dev_ctl: the finish queue when every enqueued bulk round ran (written by generate)
-    const FrameParams* Pd; // this frame's FrameParams in device memory (W.d_params)
-    // own pixel index -> image pixel (own_pixel): tiles tile_id % nranks == rank of tile x tile pixels
-    FastDiv spp_div, tile_px_div, tiles_x_div;   // by spp, tile * tile, tiles per row
-    int tile, rank, nranks;
-};
 
 // own pixel index -> image coordinates (tiles tile_id % nranks == rank, Morton order in a tile)
 __device__ __forceinline__ void own_pixel(const WfParams& Q, uint32_t i, int& px, int& py) {
@@ -220,19 +172,9 @@ __device__ __forceinline__ void own_pixel(const WfParams& Q, uint32_t i, int& px
     py = (int)(ty * T + ly);
 }
 
-// counter slots (cslot): [q*8 + shard] ray queues q = 0, 1; [16 + shard] shadow queue; [24] extra allocator
-constexpr int kCntShadowQ = 16;
-constexpr int kCntExtra = 24;
-// [66..73] per-XCD chunk counters of the finish launch: XCD k takes chunks k, k + 8, k + 16, ...
-// of the finish queue (its long-first order kept chip-wide).  One counter for the whole chip
-// serialised the grabs: 3.4M paths in chunks of 32 were ~105K returning atomics on one line.
-constexpr int kCntChunkFinish = 66;
+// counter slots only the kernels use (the others: rt_wavefront.h)
 constexpr int kCntSorted = 26;                 // hits the sort kept (misses dropped) = shade's input size
 constexpr uint32_t kNoKey = 0xffffffffu;       // sort key of a miss (dropped by the sort)
-constexpr int kCntDiagSegs = 27, kCntDiagIters = 28, kCntDiagTime = 29;   // wf_finish diagnostics
-// dev_ctl: [30] tail mode (set by the first extend launch that found fewer than `tail` live
-// paths; later bulk launches of the pass return at once), [31] the queue the finish launch reads
-constexpr int kCntTailMode = 30, kCntFinishQ = 31;
 
 // Device-clock span of a launch (WfFrameStats::trace_dev_ms): block 0 records the start, the last
 // wave of every block its end, as a max on its XCD's line (`done`: an LDS wave counter zeroed
@@ -257,8 +199,6 @@ __device__ __forceinline__ void stat_add(const WfParams& Q, int word, uint32_t v
 __device__ __forceinline__ bool tail_mode(const WfParams& Q) {
     return Q.dev_ctl && __builtin_amdgcn_readfirstlane(Q.W.counts[cslot(kCntTailMode)]) != 0u;
 }
-constexpr int kCntChunkExtend = 32;   // 8 per-XCD chunk counters each
-constexpr int kCntChunkConnect = 40;
 
 // Inclusive prefix of a sharded queue's segment counts, loaded once per kernel (uniform, so the
 // loads are scalar and the lookups below stay in registers).
@@ -281,7 +221,6 @@ __device__ __forceinline__ ShardPrefix load_prefix(const uint32_t* cnt, uint32_t
 // takes the queue front parts first, starts the long glass paths before the short ones (they
 // would otherwise set the end of its launch).  Primary rays (generate, extra samples) go to the
 // front.  Counters: L in [q * 8 + k], S in [kCntBack + q * 8 + k].
-constexpr int kCntBack = 50;
 struct QueueShards {
     uint32_t L[kShards], S[kShards];
 };
@@ -595,7 +534,6 @@ __device__ __forceinline__ float4 ld_stream(const float4* p) {
     const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ float4 ld_shade(const float4* p) { return ld_stream(p); }
 template <bool FULL, bool SORTED>
 __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur) {
     const FrameParams& P = *Pp;   // per-frame parameters in device memory
@@ -653,9 +591,9 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
                 ce = 4 * (size_t)g + 3;
             } else {
                 const uint32_t e = ebase + seg_pos(g, lk, Q.seg_cap);
-                o = ld_shade(&qin[2 * (size_t)e]);
-                d = ld_shade(&qin[2 * (size_t)e + 1]);
-                hv = ld_shade(&Q.W.hits[e]);
+                o = ld_stream(&qin[2 * (size_t)e]);
+                d = ld_stream(&qin[2 * (size_t)e + 1]);
+                hv = ld_stream(&Q.W.hits[e]);
                 ce = e;
             }
             pid = __float_as_uint(o.w);
@@ -667,7 +605,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
             if (h.id != 0xffffffffu) {                                           // miss -> path ends (:321-322)
                 const uint32_t state = __float_as_uint(d.w);
                 const float4 c = state == 0u ? make_float4(1.0f, 1.0f, 1.0f, 0.0f)
-                                             : (SORTED ? Q.W.sorted[ce] : ld_shade(&Q.W.qc[cur][ce]));
+                                             : (SORTED ? Q.W.sorted[ce] : ld_stream(&Q.W.qc[cur][ce]));
                 // a continuation ray past bounce 0 carries its Halton index in qc.w: the pixel and sample
                 // (and the per-pixel random offset behind them) are read only at bounce 0 (:342-389)
                 uint4 meta;
@@ -1577,30 +1515,7 @@ __global__ void __launch_bounds__(kBlock) wf_resolve(DevScene S, const FramePara
     P.accum_out[pix] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 
-// Segment k only receives entries from blocks b == k (mod 8): at most n/8 + 256 per pass over n
-// inputs, and (own pixels/8 + 256) * maxExtra from the extra-sample pass.
-size_t wavefront_queue_entries(size_t paths, int max_extra) {
-    return (size_t)kShards * (paths / kShards + 4096 + 256 * (size_t)max_extra);
-}
-
-static unsigned grid_for(uint32_t n, unsigned cap) {
-    unsigned g = (unsigned)(((uint64_t)n + kBlock - 1) / kBlock);
-    if (g > cap) g = cap;
-    g = (g + kShards - 1) / kShards * kShards;  // multiple of 8: segment bound (see header)
-    return g == 0 ? kShards : g;
-}
-
-#define WF_CHECK(expr)                                                                  \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            static thread_local char msg_[192];                                         \
-            snprintf(msg_, sizeof msg_, "%.120s: %s", #expr, hipGetErrorString(e_));  \
-            *err = msg_;                                                                \
-            return false;                                                               \
-        }                                                                               \
-    } while (0)
-
+// ---- the kernel instances, handed to the scheduler (rt_wavefront_host.cpp) ---------------------------
 // resident blocks (CUs x blocks per CU) of a persistent kernel
 template <typename K>
 static unsigned resident_grid(K kernel, int fallback_per_cu) {
@@ -1611,599 +1526,28 @@ static unsigned resident_grid(K kernel, int fallback_per_cu) {
     return (unsigned)(cus * per);
 }
 
-// resident blocks of the persistent traversal kernel, queried once
-// the bulk traversal launches: Q.trace_frac percent of the resident grid, a multiple of 8 (XCDs)
-static unsigned trace_grid_cap(const WfParams& Q) {
-    static const unsigned cap = resident_grid(wf_trace<false, false>, 4);
-    return std::max(8u, cap * (unsigned)std::max(Q.trace_frac, 1) / 100u / 8u * 8u);
+template <bool COUNT, bool FULL, bool SORTED, bool TEAM>
+static WfKernels kernel_set() {
+    WfKernels K = {wf_trace<false, COUNT>, wf_trace<true, COUNT>, wf_finish_step<COUNT, FULL, TEAM>,   // extend, connect, finish
+                   wf_shade<FULL, SORTED>, wf_extra, wf_resolve, wf_generate, wf_motion,
+                   wf_sort_hist, wf_sort_scatter, wf_sort_rowscan, 0u, 0u};
+    // the team instance is sized by its own occupancy (its LDS and registers differ)
+    K.finish_resident = resident_grid(K.finish, 2);
+    return K;
 }
 
-// the finish launch: Q.finish_frac percent of the resident grid (frames in flight: the rest of the
-// machine stays free for the other frames' kernels)
-template <bool COUNT, bool FULL, bool TEAM>
-static unsigned finish_full_cap() {   // resident blocks of the finish kernel instance, queried once
-    static const unsigned c = resident_grid(wf_finish_step<COUNT, FULL, TEAM>, 2);
-    return c;
-}
-template <bool COUNT, bool FULL>
-static void launch_finish(const DevScene& S, const WfParams& Q, int cur, uint32_t n, hipStream_t stream, int ts) {
-    // at least one block per XCD: each takes the chunks of its XCD's counter (wf_finish_step).
-    // Q.team: the kernel with the team drain (a separate instance: its code would raise the plain
-    // kernel's register pressure), sized by its own occupancy (its LDS and registers differ)
-    if (Q.team) {
-        const unsigned cap = std::max(8u, finish_full_cap<COUNT, FULL, true>() * (unsigned)Q.finish_frac / 100u);
-        hipLaunchKernelGGL((wf_finish_step<COUNT, FULL, true>), dim3(std::max(8u, grid_for(n, cap))), dim3(kBlock), 0,
-                           stream, S, Q.Pd, Q, cur, ts);
-    } else {
-        const unsigned cap = std::max(8u, finish_full_cap<COUNT, FULL, false>() * (unsigned)Q.finish_frac / 100u);
-        hipLaunchKernelGGL((wf_finish_step<COUNT, FULL, false>), dim3(std::max(8u, grid_for(n, cap))), dim3(kBlock), 0,
-                           stream, S, Q.Pd, Q, cur, ts);
-    }
+template <size_t... I>
+static std::array<WfKernels, 16> kernel_table(std::index_sequence<I...>) {
+    std::array<WfKernels, 16> t = {{kernel_set<(I >> 3) & 1, (I >> 2) & 1, (I >> 1) & 1, I & 1>()...}};
+    const unsigned trace = resident_grid(t[0].extend, 4);   // every traversal launch is sized by the plain extend instance
+    for (WfKernels& k : t) k.trace_resident = trace;
+    return t;
 }
 
-static void launch_finish_any(const DevScene& S, const WfParams& Q, bool count, bool full, int cur, uint32_t n,
-                              hipStream_t stream, int ts = -1) {
-    if (count) full ? launch_finish<true, true>(S, Q, cur, n, stream, ts) : launch_finish<true, false>(S, Q, cur, n, stream, ts);
-    else full ? launch_finish<false, true>(S, Q, cur, n, stream, ts) : launch_finish<false, false>(S, Q, cur, n, stream, ts);
-}
-
-static uint32_t queue_total(const uint32_t* h, int q) {   // q = 0, 1: a ray queue (both ends); 2: the shadow queue
-    uint32_t s = 0;
-    for (int k = 0; k < kShards; ++k) s += h[cslot(q * kShards + k)] + (q < 2 ? h[cslot(kCntBack + q * kShards + k)] : 0u);
-    return s;
-}
-
-// Host-driven rounds (RT_WF_HOST=1 / RT_WF_LOG=1, and the bulk-only test configuration tail <= 1):
-// every round's queue size is read back before the next launch.
-static bool iterate(const DevScene& S, const FrameParams& P, WfParams& Q, int& cur, uint32_t n, bool count, bool full,
-                    hipStream_t stream, WfFrameStats* fs, const char** err) {
-    float* stage_ms = fs->stage_ms;
-    const int max_it = P.U.maxBounces * (P.U.maxBounces + 1) + 2;
-    WavefrontBuffers& W = Q.W;
-    for (int it = 0; it < max_it && n > 0; ++it) {
-        if (n < Q.tail) {   // the rest of the pass in one persistent finish launch
-            WF_CHECK(hipEventRecord(W.ev[0], stream));
-            WF_CHECK(hipMemsetAsync(W.counts + cslot(kCntChunkFinish), 0, cslot(kShards) * sizeof(uint32_t), stream));
-            if (Q.diag) {
-                WF_CHECK(hipMemsetAsync(W.counts + kWfDiagHist, 0, 64 * sizeof(uint32_t), stream));
-                WF_CHECK(hipMemsetAsync(W.counts + kWfDiagExh, 0, 64 * sizeof(uint32_t), stream));
-                WF_CHECK(hipMemsetAsync(W.counts + kWfStat + kStatDiagShadeT, 0, (kWfStatWords - kStatDiagShadeT) * sizeof(uint32_t),
-                                        stream));
-            }
-            launch_finish_any(S, Q, count, full, cur, n, stream);
-            WF_CHECK(hipGetLastError());
-            WF_CHECK(hipEventRecord(W.ev[1], stream));
-            WF_CHECK(hipMemcpyAsync(W.h_counts, W.counts, kWfCountWords * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                    stream));
-            WF_CHECK(hipStreamSynchronize(stream));
-            float a = 0;
-            WF_CHECK(hipEventElapsedTime(&a, W.ev[0], W.ev[1]));
-            stage_ms[5] += a;
-            ++fs->finish_launches;
-            ++fs->iterations;
-            if (Q.diag) {
-                fprintf(stderr, "[wf] it %d finish paths %u  %.3f ms; longest path %u segments, "
-                        "slowest wave %u iterations in %.3f ms\n", it, n, a, W.h_counts[cslot(kCntDiagSegs)],
-                        W.h_counts[cslot(kCntDiagIters)], W.h_counts[cslot(kCntDiagTime)] * 1e-5);
-                const double st = W.h_counts[kWfStat + kStatDiagShadeT], tt = W.h_counts[kWfStat + kStatDiagTotalT];
-                const double np = W.h_counts[kWfStat + kStatDiagPasses], ns = W.h_counts[kWfStat + kStatDiagShaded];
-                fprintf(stderr, "[wf] finish: %.1f %% of wave time in shading passes, %.0f passes, %.1f lanes per pass\n",
-                        tt > 0 ? 100.0 * st / tt : 0.0, np, np > 0 ? ns / np : 0.0);
-                for (int cl = 0; cl < 18; ++cl) {
-                    uint32_t tot = 0;
-                    double sum = 0;
-                    for (int b = 0; b < 32; ++b) {
-                        tot += W.h_counts[kWfDiagLen + cl * 32 + b];
-                        sum += (double)b * W.h_counts[kWfDiagLen + cl * 32 + b];
-                    }
-                    if (!tot) continue;
-                    fprintf(stderr, "[wf] finish paths entering at bounce %d%s: %u, segments mean %.2f:", cl % 9,
-                            cl >= 9 ? " refracting" : "", tot, sum / tot);
-                    for (int b = 0; b < 32; ++b)
-                        if (W.h_counts[kWfDiagLen + cl * 32 + b]) fprintf(stderr, " %d:%u", b, W.h_counts[kWfDiagLen + cl * 32 + b]);
-                    fprintf(stderr, "\n");
-                }
-                fprintf(stderr, "[wf] finish wave end times (50 us bins):");
-                for (int b = 0; b < 64; ++b)
-                    if (W.h_counts[kWfDiagHist + b]) fprintf(stderr, " %d:%u", b, W.h_counts[kWfDiagHist + b]);
-                fprintf(stderr, "\n[wf] finish queue exhausted at (50 us bins):");
-                for (int b = 0; b < 64; ++b)
-                    if (W.h_counts[kWfDiagExh + b]) fprintf(stderr, " %d:%u", b, W.h_counts[kWfDiagExh + b]);
-                const double ip = W.h_counts[kWfStat + kStatDiagItPre], ix = W.h_counts[kWfStat + kStatDiagItPost];
-                const double tp = W.h_counts[kWfStat + kStatDiagTPre], tx = W.h_counts[kWfStat + kStatDiagTPost];
-                const double lx = W.h_counts[kWfStat + kStatDiagLanesPost];
-                double waves = 0;
-                for (int b = 0; b < 64; ++b) waves += W.h_counts[kWfDiagHist + b];
-                waves = waves > 0 ? waves : 1;
-                fprintf(stderr, "\n[wf] finish per wave: %.0f iterations at %.2f us before its queue ran out, %.0f at %.2f us "
-                        "after (%.1f active lanes)\n", ip / waves, ip > 0 ? tp * 0.01 / ip : 0.0, ix / waves,
-                        ix > 0 ? tx * 0.01 / ix : 0.0, ix > 0 ? lx / ix : 0.0);
-            }
-            return true;
-        }
-        int next = 1 - cur;
-        WF_CHECK(hipEventRecord(W.ev[0], stream));
-        unsigned g = grid_for(n, Q.shade_blocks);
-        unsigned gt = grid_for(n, trace_grid_cap(Q));
-        if (count) hipLaunchKernelGGL((wf_trace<false, true>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, -1);
-        else hipLaunchKernelGGL((wf_trace<false, false>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, -1);
-        WF_CHECK(hipEventRecord(W.ev[1], stream));
-        const bool sort = Q.sort_bins != 0;
-        if (sort) {
-            hipLaunchKernelGGL(wf_sort_hist, dim3(kSortBlocks), dim3(kSortThreads), 0, stream, S, Q, cur);
-            hipLaunchKernelGGL(wf_sort_rowscan, dim3(Q.sort_bins), dim3(kSortBlocks), 0, stream, Q);
-            hipLaunchKernelGGL(wf_sort_scatter, dim3(kSortBlocks), dim3(kSortThreads), 0, stream, S, Q, cur);
-        }
-        WF_CHECK(hipEventRecord(W.ev[4], stream));
-        if (full) {
-            if (sort) hipLaunchKernelGGL((wf_shade<true, true>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-            else hipLaunchKernelGGL((wf_shade<true, false>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-        } else {
-            if (sort) hipLaunchKernelGGL((wf_shade<false, true>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-            else hipLaunchKernelGGL((wf_shade<false, false>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-        }
-        WF_CHECK(hipEventRecord(W.ev[2], stream));
-        if (count) hipLaunchKernelGGL((wf_trace<true, true>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, -1);
-        else hipLaunchKernelGGL((wf_trace<true, false>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, -1);
-        WF_CHECK(hipGetLastError());
-        WF_CHECK(hipEventRecord(W.ev[3], stream));
-        WF_CHECK(hipMemcpyAsync(W.h_counts, W.counts, kWfCountWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        WF_CHECK(hipStreamSynchronize(stream));
-        float a = 0, b = 0, c = 0, srt = 0;
-        WF_CHECK(hipEventElapsedTime(&a, W.ev[0], W.ev[1]));
-        WF_CHECK(hipEventElapsedTime(&srt, W.ev[1], W.ev[4]));
-        WF_CHECK(hipEventElapsedTime(&b, W.ev[4], W.ev[2]));
-        WF_CHECK(hipEventElapsedTime(&c, W.ev[2], W.ev[3]));
-        stage_ms[1] += a;
-        stage_ms[6] += srt;
-        stage_ms[2] += b;
-        stage_ms[3] += c;
-        fs->trace_rays += (unsigned long long)n + queue_total(W.h_counts, 2);  // extend + connect rays
-        fs->trace_closest_rays += n;
-        fs->trace_launches += 2;
-        fs->trace_ms += a + c;
-        if (Q.diag) {
-            fprintf(stderr, "[wf] it %d rays %u shadow %u  extend %.3f sort %.3f shade %.3f connect %.3f ms\n", it, n,
-                    queue_total(W.h_counts, 2), a, srt, b, c);
-            if (count) {
-                for (int any = 0; any < 2; ++any) {
-                    fprintf(stderr, "[wf]   %s steps/ray log2 bins (max %u):", any ? "connect" : "extend",
-                            W.h_counts[kWfDiagSteps + 64 + any]);
-                    for (int b2 = 0; b2 < 32; ++b2)
-                        if (W.h_counts[kWfDiagSteps + 32 * any + b2])
-                            fprintf(stderr, " %d:%u", b2, W.h_counts[kWfDiagSteps + 32 * any + b2]);
-                    fprintf(stderr, "\n");
-                }
-                WF_CHECK(hipMemsetAsync(W.counts + kWfDiagSteps, 0, 66 * sizeof(uint32_t), stream));
-            }
-        }
-        n = queue_total(W.h_counts, next);
-        cur = next;
-        ++fs->iterations;
-    }
-    return true;
-}
-
-// ---- device-side control: the whole frame enqueued without host round trips ------------------------
-// The host enqueues `rounds_for(paths)` bulk rounds per pass (enough for the live paths to fall
-// below the finish threshold when about half of them end per round), then one finish launch;
-// the extend launch of a round that finds fewer than `tail` live paths flags tail mode and
-// names its queue as the finish input, and every later bulk launch of the pass returns at once.
-// Per-stage times come from events between the launches, ray counts and rounds from device
-// counters; both are collected by wavefront_collect once the frame has finished.
-namespace {
-// Whether the HIP runtime takes timeline events inside a captured frame (external event-record
-// nodes).  The system ROCm 7.2 runtime the C host links does; the HIP runtime PyTorch bundles
-// refuses them (hipEventRecordWithFlags(..., hipEventRecordExternal) during capture: invalid
-// argument), so after the first refusal frames are captured without them: the graphs then hold
-// the frame's launches, memsets and copies only, and the per-stage times of replayed frames are
-// not recorded (rt_stats kernel_ms; the frame's own time, taken outside the graphs, is).
-// Process-wide and one-way (true -> false) for g_graph_events; g_ext_refused is the refusal flag of a
-// capture attempt.  Atomics: contexts on other threads may capture concurrently (ThreadLocal capture).
-static std::atomic<bool> g_graph_events{true};
-static thread_local bool g_ext_refused = false;   // set when this thread's capture had an external event record refused
-
-struct Enqueue {
-    WfTimeline& T;
-    hipStream_t stream;
-    bool capture;   // recording into a HIP graph: events and cross-stream waits are external nodes
-    int last = -1;
-    bool mark(const char** err) {
-        if (capture && !g_graph_events) return true;   // untimed capture
-        if (T.n_ev >= WfTimeline::kMaxEv) {
-            *err = "wavefront timeline: too many events";
-            return false;
-        }
-        const hipError_t e = hipEventRecordWithFlags(T.ev[T.n_ev], stream, capture ? hipEventRecordExternal : 0u);
-        if (e != hipSuccess) {
-            if (capture) g_ext_refused = true;
-            static thread_local char msg[160];
-            snprintf(msg, sizeof msg, "hipEventRecordWithFlags(%s): %s", capture ? "external" : "0", hipGetErrorString(e));
-            *err = msg;
-            return false;
-        }
-        last = T.n_ev++;
-        return true;
-    }
-    // closes the span [previous mark, now) as `stage`; without a previous mark (part 0 was captured
-    // untimed and this part is recorded eagerly) it only marks: there is no start event to time from
-    bool span(int stage, const char** err) {
-        if (capture && !g_graph_events) return true;
-        const int a = last;
-        if (!mark(err)) return false;
-        if (a >= 0) T.spans[T.n_spans++] = WfTimeline::Span{stage, a, last};
-        return true;
-    }
-};
-}  // namespace
-
-static int rounds_for(uint64_t paths, uint32_t tail) {
-    if (paths < tail) return 0;
-    int k = 2;
-    while (k < 16 && (paths >> (k - 1)) >= tail) ++k;
-    return k;
-}
-
-static bool enqueue_pass(const DevScene& S, const FrameParams& P, const WfParams& Q, int rounds, bool count, bool full,
-                         int ts, Enqueue& E, const char** err) {
-    hipStream_t stream = E.stream;
-    if (!Q.spans) ts = -1;   // no device-clock spans: the kernels skip the stamps
-    const unsigned gt = trace_grid_cap(Q), g = Q.shade_blocks;
-    for (int k = 0; k < rounds; ++k) {
-        const int cur = k & 1;
-        const bool kHitSort = Q.sort_bins != 0;
-        if (count) hipLaunchKernelGGL((wf_trace<false, true>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, ts + 2 * k);
-        else hipLaunchKernelGGL((wf_trace<false, false>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, ts + 2 * k);
-        if (!E.span(1, err)) return false;
-        if (kHitSort) {
-            hipLaunchKernelGGL(wf_sort_hist, dim3(kSortBlocks), dim3(kSortThreads), 0, stream, S, Q, cur);
-            hipLaunchKernelGGL(wf_sort_rowscan, dim3(Q.sort_bins), dim3(kSortBlocks), 0, stream, Q);
-            hipLaunchKernelGGL(wf_sort_scatter, dim3(kSortBlocks), dim3(kSortThreads), 0, stream, S, Q, cur);
-            if (!E.span(6, err)) return false;
-        }
-        if (full) {
-            if (kHitSort) hipLaunchKernelGGL((wf_shade<true, true>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-            else hipLaunchKernelGGL((wf_shade<true, false>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-        } else {
-            if (kHitSort) hipLaunchKernelGGL((wf_shade<false, true>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-            else hipLaunchKernelGGL((wf_shade<false, false>), dim3(g), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-        }
-        if (!E.span(2, err)) return false;
-        if (count) hipLaunchKernelGGL((wf_trace<true, true>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, ts + 2 * k + 1);
-        else hipLaunchKernelGGL((wf_trace<true, false>), dim3(gt), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur, ts + 2 * k + 1);
-        if (!E.span(3, err)) return false;
-    }
-    // the finish chunk counter is zero here: the frame start clears every counter and the
-    // extra-sample pass clears it again before its own finish launch
-    launch_finish_any(S, Q, count, full, -1, 1u << 30, stream, ts + kTsFinish);   // resident grid; input queue from the counters
-    WF_CHECK(hipGetLastError());
-    return E.span(5, err);
-}
-
-// One frame on `stream` in two parts: record_base = the base pass and the motion vectors,
-// record_rest = the extra-sample pass and the resolve, which read the previous frame's outputs
-// (the caller enqueues the wait for it in between).  Launch arguments come from S, Q and the
-// buffer pointers in P; the per-frame values of P are read by the kernels from Q.Pd.
-static bool record_base(const DevScene& S, const FrameParams& P, WfParams& Q, bool count, bool full,
-                        hipStream_t stream, WfTimeline& T, bool capture, const char** err) {
-    WavefrontBuffers& W = Q.W;
-    Enqueue E{T, stream, capture};
-    T.n_ev = T.n_spans = 0;
-    if (!E.mark(err)) return false;
-    // counters, and the launch-span stamps when they are recorded
-    T.dev_spans = Q.spans != 0;
-    WF_CHECK(hipMemsetAsync(W.counts, 0, Q.spans ? kWfCountAllocBytes : kWfTsOffset, stream));
-    const int rounds = rounds_for(Q.base_paths, Q.tail);
-    Q.finish_q = rounds & 1;
-    hipLaunchKernelGGL(wf_generate, dim3(grid_for(Q.base_paths, 16384)), dim3(kBlock), 0, stream, S, Q.Pd, Q);
-    WF_CHECK(hipGetLastError());
-    if (!E.span(0, err)) return false;
-    if (!enqueue_pass(S, P, Q, rounds, count, full, 0, E, err)) return false;
-    hipLaunchKernelGGL(wf_motion, dim3(grid_for(Q.own_pixels, 1u << 30)), dim3(kBlock), 0, stream, S, Q.Pd, Q);
-    WF_CHECK(hipGetLastError());
-    return E.span(4, err);
-}
-
-static bool record_rest(const DevScene& S, const FrameParams& P, WfParams& Q, bool count, bool full, int maxExtra,
-                        bool with_extra, hipStream_t stream, WfTimeline& T, bool capture, const char** err) {
-    WavefrontBuffers& W = Q.W;
-    Enqueue E{T, stream, capture};
-    E.last = T.n_ev - 1;   // spans continue from record_base's last event
-    if (with_extra) {
-        // second pass over the motion-adaptive extra samples (:779-789), appended to queue 0
-        const int rounds2 = rounds_for((uint64_t)Q.own_pixels * (uint64_t)maxExtra, Q.tail);
-        WF_CHECK(hipMemsetAsync(W.counts, 0, cslot(kShards) * sizeof(uint32_t), stream));
-        WF_CHECK(hipMemsetAsync(W.counts + cslot(kCntBack), 0, cslot(kShards) * sizeof(uint32_t), stream));
-        WF_CHECK(hipMemsetAsync(W.counts + cslot(kCntChunkExtend), 0, cslot(2 * kShards) * sizeof(uint32_t), stream));
-        WF_CHECK(hipMemsetD32Async(W.counts + cslot(kCntTailMode), 0u, 1, stream));
-        WF_CHECK(hipMemsetD32Async(W.counts + cslot(kCntFinishQ), (uint32_t)(rounds2 & 1), 1, stream));
-        WF_CHECK(hipMemsetAsync(W.counts + cslot(kCntChunkFinish), 0, cslot(kShards) * sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(wf_extra, dim3(grid_for(Q.own_pixels, 1u << 30)), dim3(kBlock), 0, stream, S, Q.Pd, Q, 0);
-        WF_CHECK(hipGetLastError());
-        if (!E.span(4, err)) return false;
-        if (!enqueue_pass(S, P, Q, rounds2, count, full, kTsPass, E, err)) return false;
-    }
-    hipLaunchKernelGGL(wf_resolve, dim3(grid_for(Q.own_pixels, 1u << 30)), dim3(kBlock), 0, stream, S, Q.Pd, Q,
-                       with_extra ? 1 : 0);
-    WF_CHECK(hipGetLastError());
-    if (!E.span(4, err)) return false;
-    WF_CHECK(hipMemcpyAsync(W.h_counts, W.counts, Q.spans ? kWfCountAllocBytes : kWfTsOffset, hipMemcpyDeviceToHost,
-                            stream));
-    return true;
-}
-
-static bool record_part(const DevScene& S, const FrameParams& P, WfParams& Q, bool count, bool full, int maxExtra,
-                        bool with_extra, int part, hipStream_t stream, WfTimeline& T, bool capture, const char** err) {
-    return part == 0 ? record_base(S, P, Q, count, full, stream, T, capture, err)
-                     : record_rest(S, P, Q, count, full, maxExtra, with_extra, stream, T, capture, err);
-}
-
-
-// part `part` of the frame (record_part), eagerly or captured into T.exec[part] and launched
-static bool capture_part(const DevScene& S, const FrameParams& P, WfParams& Q, bool count, bool full, int maxExtra,
-                         bool with_extra, int part, hipStream_t stream, WfTimeline& T, bool rebuild, const char** err) {
-    if (rebuild) {
-        const char* rerr = nullptr;
-        hipGraph_t g = nullptr;
-        const int n_ev = T.n_ev, n_spans = T.n_spans;
-        hipError_t be, ce, ie;
-        bool ok;
-        for (int attempt = 0;; ++attempt) {
-            g_ext_refused = false;
-            be = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
-            ok = be == hipSuccess && record_part(S, P, Q, count, full, maxExtra, with_extra, part, stream, T, true, &rerr);
-            ce = be == hipSuccess ? hipStreamEndCapture(stream, &g) : be;
-            ie = hipErrorUnknown;
-            if (ok && ce == hipSuccess && g) ie = hipGraphInstantiateWithFlags(&T.exec[part], g, 0);
-            if (g) (void)hipGraphDestroy(g);
-            g = nullptr;
-            if (!ok && g_ext_refused && g_graph_events && attempt == 0) {
-                // this runtime takes no timeline events in a graph: capture untimed from now on
-                (void)hipGetLastError();
-                g_graph_events = false;
-                T.n_ev = n_ev;
-                T.n_spans = n_spans;
-                continue;
-            }
-            break;
-        }
-        if (!ok || ce != hipSuccess || ie != hipSuccess) {
-            // capture refused (an API the runtime cannot capture): this slot renders eagerly from now on
-            // (rt_stats total_graph_fallbacks counts its frames; the first refusal is reported here)
-            static bool reported = false;
-            if (!reported) {
-                reported = true;
-                fprintf(stderr, "rt: frame graph capture (part %d) refused: begin %s, record %s, end %s, instantiate %s; "
-                        "the slot renders eagerly\n", part, hipGetErrorString(be), ok ? "ok" : (rerr ? rerr : "?"),
-                        hipGetErrorString(ce), hipGetErrorString(ie));
-            }
-            (void)hipGetLastError();
-            T.exec[part] = nullptr;
-            T.graph_failed = true;
-            T.n_ev = n_ev;
-            T.n_spans = n_spans;
-            return record_part(S, P, Q, count, full, maxExtra, with_extra, part, stream, T, false, err);
-        }
-    }
-    WF_CHECK(hipGraphLaunch(T.exec[part], stream));
-    return true;
-}
-
-static bool enqueue_wavefront(const DevScene& S, const FrameParams& P, WfParams& Q, bool count, bool full,
-                              int maxExtra, bool extra_pass, hipStream_t stream, hipEvent_t prev_done, WfTimeline& T,
-                              const char** err, bool graphs) {
-    Q.dev_ctl = 1;
-    Q.finish_q = 0;   // set by record_base from the round count
-    const bool with_extra = maxExtra > 0 && extra_pass;
-    if (!graphs || T.graph_failed) {
-        T.graph_mode = graphs ? kGraphFallback : kGraphEager;
-        if (!record_base(S, P, Q, count, full, stream, T, false, err)) return false;
-        if (prev_done) WF_CHECK(hipStreamWaitEvent(stream, prev_done, 0));
-        if (!record_rest(S, P, Q, count, full, maxExtra, with_extra, stream, T, false, err)) return false;
-        T.pending = true;
-        return true;
-    }
-    // The frame's launches, memsets and copies only take S, Q (by value) and the slot's fixed
-    // buffers and events; everything that changes per frame is in the device FrameParams, uploaded
-    // before the launch.  So the graph is valid while these bytes are.
-    std::vector<uint8_t> key(sizeof(DevScene) + sizeof(WfParams) + 4 * sizeof(int));
-    {
-        WfParams Qk = Q;
-        Qk.W.param_slot = 0;   // the upload ring position is host bookkeeping
-        uint8_t* k = key.data();
-        std::memcpy(k, &S, sizeof S);
-        std::memcpy(k + sizeof S, &Qk, sizeof Qk);
-        const int flags[4] = {count ? 1 : 0, full ? 1 : 0, with_extra ? 1 : 0, maxExtra};
-        std::memcpy(k + sizeof S + sizeof Qk, flags, sizeof flags);
-    }
-    const bool rebuild = !T.exec[0] || !T.exec[1] || T.key != key;
-    if (rebuild) {
-        // the slot's previous frame has finished (its slot was harvested): its graphs can go
-        for (hipGraphExec_t& x : T.exec)
-            if (x) {
-                WF_CHECK(hipGraphExecDestroy(x));
-                x = nullptr;
-            }
-        T.key.clear();
-    }
-    if (!capture_part(S, P, Q, count, full, maxExtra, with_extra, 0, stream, T, rebuild, err)) return false;
-    if (prev_done) WF_CHECK(hipStreamWaitEvent(stream, prev_done, 0));
-    if (T.graph_failed) {   // part 0 could not be captured
-        if (!record_rest(S, P, Q, count, full, maxExtra, with_extra, stream, T, false, err)) return false;
-    } else if (!capture_part(S, P, Q, count, full, maxExtra, with_extra, 1, stream, T, rebuild, err)) {
-        return false;
-    }
-    if (rebuild && !T.graph_failed) T.key.swap(key);
-    T.graph_mode = T.graph_failed ? kGraphFallback : rebuild ? kGraphCapture : kGraphReplay;
-    T.pending = true;
-    return true;
-}
-
-bool wavefront_collect(const WavefrontBuffers& W, WfTimeline& T, WfFrameStats* fs, const char** err) {
-    if (!T.pending) return true;
-    T.pending = false;
-    *fs = WfFrameStats{};
-    for (int i = 0; i < T.n_spans; ++i) {
-        const WfTimeline::Span& sp = T.spans[i];
-        float ms = 0.0f;
-        WF_CHECK(hipEventElapsedTime(&ms, T.ev[sp.a], T.ev[sp.b]));
-        fs->stage_ms[sp.stage] += ms;
-        if (sp.stage == 1 || sp.stage == 3) fs->trace_ms += ms;
-    }
-    fs->iterations = (int)W.h_counts[kWfStat + kStatRounds];
-    fs->trace_launches = (int)W.h_counts[kWfStat + kStatTraceLaunches];
-    fs->trace_rays = W.h_counts[kWfStat + kStatTraceRays];
-    fs->trace_closest_rays = W.h_counts[kWfStat + kStatExtendRays];
-    fs->finish_launches = (int)W.h_counts[kWfStat + kStatFinish];
-    fs->graph_mode = T.graph_mode;
-    for (int pass = 0; pass < (T.dev_spans ? 2 : 0); ++pass)   // device-clock spans (10 ns ticks) of the launches that ran
-        for (int k = 0; k <= kTsFinish; ++k) {
-            const int slot = pass * kTsPass + k;
-            const unsigned long long a = W.h_tstamp[slot * kTsStride];
-            unsigned long long b = 0;
-            for (int x = 1; x <= 8; ++x) b = std::max(b, W.h_tstamp[slot * kTsStride + kTsLine * x]);
-            if (a == 0 || b <= a) continue;
-            const float ms = (float)((double)(b - a) * 1e-5);
-            if (k == kTsFinish) {
-                fs->finish_dev_ms += ms;
-                fs->finish_dev_launches++;
-            } else if (k < 2 * 16) {
-                fs->trace_dev_ms += ms;
-                fs->trace_dev_launches++;
-            }
-        }
-    return true;
-}
-
-bool run_wavefront(const DevScene& S, const FrameParams& P, WavefrontBuffers& W, const WfTuning& tu, int own_tiles,
-                   bool count, bool spans, int tail_paths, int sort_bins, bool extra_pass, int in_flight,
-                   hipStream_t stream, hipEvent_t prev_done, WfTimeline* tl, WfFrameStats* fs, const char** err,
-                   bool graphs) {
-    WfParams Q;
-    std::memset(&Q, 0, sizeof Q);   // no stray padding bytes (frame-graph key)
-    Q.W = W;
-    Q.spp = max(P.U.samplesPerPixel, 1);
-    Q.own_pixels = (uint32_t)own_tiles * (uint32_t)P.tile_size * (uint32_t)P.tile_size;
-    Q.base_paths = Q.own_pixels * (uint32_t)Q.spp;
-    Q.seg_cap = (uint32_t)(W.queue_entries / kShards);
-    Q.refill_min = tu.refill_min;
-    Q.chunk = tu.chunk;
-    Q.tail = tail_paths > 0 ? (uint32_t)tail_paths : tu.tail;
-    Q.sort_bins = (uint32_t)sort_bins;
-    Q.diag = tu.log;
-    Q.shade_min = tu.shade_min;
-    Q.shade_min_x = tu.shade_min_x;
-    // the team drain pays where the drain is a large part of the finish: small frames (C3g rank
-    // shares, DESIGN.md §3.3: 8-way +2.3 %, 4-way +1.5 %, 2-way ±1 %, the whole 1080p frame four in
-    // flight ±0), but not the smallest (C1 256x256x1: -7.5 %)
-    Q.team = tu.team >= 0 ? tu.team : (Q.base_paths >= kTeamAutoMin && Q.base_paths <= kTeamAutoPaths ? 4 : 0);
-    Q.fchunk = tu.fchunk;
-    Q.shade_blocks = tu.shade_blocks;
-    Q.spans = spans ? 1 : 0;
-    Q.spp_div = make_fastdiv((uint32_t)Q.spp);
-    Q.tile = P.tile_size;
-    Q.rank = P.rank;
-    Q.nranks = P.nranks;
-    Q.tile_px_div = make_fastdiv((uint32_t)P.tile_size * (uint32_t)P.tile_size);
-    Q.tiles_x_div = make_fastdiv((uint32_t)max(P.tiles_x, 1));
-    // frames in flight: the finish tail takes part of the resident grid and leaves the rest to the
-    // other frames' bulk rounds (C3g sweeps, DESIGN.md §3: two slots 40 %; four or more 20 %: C3g
-    // with four slots 20 / 25 / 33 % 8.49-8.54 / 8.21-8.50 / 8.28-8.36 Grays/s, and a multi-GPU
-    // rank's share; three 33 %); one frame at a time: all of it
-    // four or more frames in flight: the bulk traversal launches take 60 % of the resident grid,
-    // leaving CUs to the other frames' kernels (C3g 8.51-8.64 -> 8.61-8.72 Grays/s over five
-    // alternating pairs, 75 % +0.5 %; the 8-way rank share at 75 % +0.9 %); fewer frames: all of it
-    // eight frames in flight (round 6): the smaller the frame, the smaller the share, so that more
-    // frames' bulk rounds run side by side -- 20 % up to 2.5M base paths (8-way C3g rank share 7.26 ->
-    // 7.51-7.54 Grays/s, 4-way 8.59 -> 8.87-8.88; 15 % 7.46-7.49), 30 % up to 6M (2-way 9.29 ->
-    // 9.47-9.55), 40 % above (the whole C3g frame 9.74-9.83 -> 9.82-9.91; 50 % 9.80-9.81)
-    // (profiles/r06_experiments.txt)
-    Q.trace_frac = tu.trace_frac > 0 ? tu.trace_frac
-                 : in_flight >= 8 ? (Q.base_paths <= 2500000u ? 20 : Q.base_paths <= 6000000u ? 30 : 40)
-                 : in_flight >= 4 ? 60 : 100;
-    // eight frames in flight of at most 6M base paths (a multi-GPU rank's share): 12 % (round 5,
-    // after the slots stopped serialising: 8-way rank share 6.76 -> 7.02, 4-way 8.14 -> 8.44, 2-way
-    // (4.1M paths) 9.12 -> 9.35 Grays/s; 8 % +-0, 33 % -10 %; the whole C3g frame (8.3M) +-0 and
-    // configs[3]'s 16.6M-path rank share -2 %, so larger frames keep 20 %)
-    Q.finish_frac = tu.finish_frac > 0 ? tu.finish_frac
-                  : (in_flight >= 8 && Q.base_paths <= 6000000u) ? 12
-                  : in_flight >= 4 ? 20 : in_flight == 2 ? 40 : (in_flight > 1 ? 100 / in_flight : 100);
-    if (sort_bins && (sort_bins < kSortMinBins || sort_bins > kSortMaxBins || (sort_bins & (sort_bins - 1)) ||
-                      !S.tri_bin || !W.sorted)) {
-        *err = "bad hit-sort configuration";
-        return false;
-    }
-    *fs = WfFrameStats{};
-    float* stage_ms = fs->stage_ms;
-    // tail <= 1 (bulk rounds only, a test configuration) keeps the host loop: its round count is
-    // only bounded by maxBounces * (maxBounces + 1)
-    const bool dev = tl && !tu.host_ctl && !tu.log && Q.tail > 1;
-    Q.Pd = W.d_params;
-    {   // this frame's parameters -> device; the slot's previous upload has executed once its event has
-        const int slot = W.param_slot;
-        W.param_slot = (slot + 1) % WavefrontBuffers::kParamSlots;
-        WF_CHECK(hipEventSynchronize(W.param_ev[slot]));
-        W.h_params[slot] = P;
-        WF_CHECK(hipMemcpyAsync(W.d_params, &W.h_params[slot], sizeof(FrameParams), hipMemcpyHostToDevice, stream));
-        WF_CHECK(hipEventRecord(W.param_ev[slot], stream));
-    }
-    const bool full = needs_full(P.U, S);
-    const int maxExtra = (P.U.enableMotionAdaptiveSampling != 0) ? max(P.U.motionSamplingMaxExtraSamples, 0) : 0;
-    if (dev) {
-        // the device queries behind the grid sizes run before a stream is capturing (a capture
-        // must hold stream work only)
-        (void)trace_grid_cap(Q);
-        (void)finish_full_cap<false, false, false>();
-        (void)finish_full_cap<false, true, false>();
-        (void)finish_full_cap<true, false, false>();
-        (void)finish_full_cap<true, true, false>();
-        (void)finish_full_cap<false, false, true>();
-        (void)finish_full_cap<false, true, true>();
-        (void)finish_full_cap<true, false, true>();
-        (void)finish_full_cap<true, true, true>();
-        return enqueue_wavefront(S, P, Q, count, full, maxExtra, extra_pass, stream, prev_done, *tl, err, graphs);
-    }
-    Q.dev_ctl = 0;
-    Q.finish_q = 0;
-
-    WF_CHECK(hipEventRecord(W.ev[0], stream));
-    WF_CHECK(hipMemsetAsync(W.counts, 0, kWfCountWords * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(wf_generate, dim3(grid_for(Q.base_paths, 16384)), dim3(kBlock), 0, stream, S, Q.Pd, Q);
-    WF_CHECK(hipGetLastError());
-    WF_CHECK(hipEventRecord(W.ev[1], stream));
-    WF_CHECK(hipMemcpyAsync(W.h_counts, W.counts, kWfCountWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    WF_CHECK(hipStreamSynchronize(stream));
-    float ms = 0;
-    WF_CHECK(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
-    stage_ms[0] += ms;
-    int cur = 0;
-    if (!iterate(S, P, Q, cur, queue_total(W.h_counts, 0), count, full, stream, fs, err)) return false;
-
-    if (prev_done) WF_CHECK(hipStreamWaitEvent(stream, prev_done, 0));
-    WF_CHECK(hipEventRecord(W.ev[0], stream));
-    hipLaunchKernelGGL(wf_motion, dim3(grid_for(Q.own_pixels, 1u << 30)), dim3(kBlock), 0, stream, S, Q.Pd, Q);
-    WF_CHECK(hipGetLastError());
-    if (maxExtra > 0) {
-        // the extra-sample pass appends primary rays to queue `cur` (reset here)
-        WF_CHECK(hipMemsetAsync(W.counts + cslot(cur * kShards), 0, cslot(kShards) * sizeof(uint32_t), stream));
-        WF_CHECK(hipMemsetAsync(W.counts + cslot(kCntBack + cur * kShards), 0, cslot(kShards) * sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(wf_extra, dim3(grid_for(Q.own_pixels, 1u << 30)), dim3(kBlock), 0, stream, S, Q.Pd, Q, cur);
-        WF_CHECK(hipGetLastError());
-        WF_CHECK(hipMemcpyAsync(W.h_counts, W.counts, kWfCountWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        WF_CHECK(hipStreamSynchronize(stream));
-        uint32_t n_extra = queue_total(W.h_counts, cur);
-        if (n_extra > 0) {
-            if (!iterate(S, P, Q, cur, n_extra, count, full, stream, fs, err)) return false;
-        }
-    }
-    hipLaunchKernelGGL(wf_resolve, dim3(grid_for(Q.own_pixels, 1u << 30)), dim3(kBlock), 0, stream, S, Q.Pd, Q,
-                       maxExtra > 0 ? 1 : 0);
-    WF_CHECK(hipGetLastError());
-    WF_CHECK(hipEventRecord(W.ev[1], stream));
-    WF_CHECK(hipStreamSynchronize(stream));
-    WF_CHECK(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
-    stage_ms[4] += ms;
-    return true;
+const WfKernels& wf_kernels(bool count, bool full, bool sorted, bool team) {
+    static const std::array<WfKernels, 16> table = kernel_table(std::make_index_sequence<16>());
+    return table[(count ? 8 : 0) | (full ? 4 : 0) | (sorted ? 2 : 0) | (team ? 1 : 0)];
 }
 
 }  // namespace rt
+

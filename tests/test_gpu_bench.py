@@ -37,7 +37,7 @@ def test_bench_line_contract():
     cb = d["cpu_baseline"]
     assert cb["value"] > 0 and cb["kind"] == "port" and cb["cores"] >= 1
     # a frame below 512K paths keeps four frames in flight although bench.py gives the process
-    # eight hardware queues (rt_api.cpp kSmallFramePaths)
+    # eight hardware queues (rt_wf_schedule.h kSmallFramePaths)
     assert d["config"]["frames_in_flight"] == 4
     _roofline_consistent(d)
     # the timed frames replay captured HIP graphs

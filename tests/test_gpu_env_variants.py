@@ -33,3 +33,18 @@ def test_env_variant_matches_golden(env):
     print(r.stdout[-3000:])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.count(" ok ") == len(CASES.split(",")) * len(PIPES.split(","))
+
+
+def test_round_log_matches_golden_and_prints():
+    """RT_WF_LOG=1: host-driven rounds with the per-round and finish diagnostics on stderr.  The
+    frames stay bit-identical to the goldens and both kinds of diagnostic line are printed."""
+    e = dict(os.environ)
+    e["RT_WF_LOG"] = "1"
+    r = subprocess.run([sys.executable, "-u", os.path.join(HERE, "env_variant_child.py"), CASES, PIPES], env=e,
+                       capture_output=True, text=True, timeout=150)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert r.stdout.count(" ok ") == len(CASES.split(",")) * len(PIPES.split(","))
+    lines = r.stderr.splitlines()
+    assert any(l.startswith("[wf] it ") for l in lines), r.stderr[-2000:]
+    assert any(l.startswith("[wf] finish:") for l in lines), r.stderr[-2000:]

@@ -97,7 +97,7 @@ def test_in_flight_then_megakernel_frame(rt, assets):
 
 
 # 0: the library default for a rank's small frame: at most four slots below 512K paths
-# (rt_api.cpp kSmallFramePaths), whatever the hardware queue count
+# (rt_wf_schedule.h kSmallFramePaths), whatever the hardware queue count
 @pytest.mark.parametrize("fif,expect", [(2, 2), (0, 4)])
 def test_in_flight_tile_gather(rt, assets, fif, expect):
     """Two ranks' renderers (tile split, frames in flight) with the per-frame gather enqueued on
