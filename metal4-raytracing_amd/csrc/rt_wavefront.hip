@@ -5,7 +5,8 @@
 //   generate  one thread per (own pixel, sample): primary ray (:270-292) -> ray queue
 //   extend    closest-hit traversal of the ray queue (:314-322)          -> hit records
 //   shade     shade_step per hit (:324-774): updates path state, appends the continuation
-//             ray to the next queue and the NEE shadow ray to the shadow queue
+//             ray to the next queue and the NEE shadow ray to the shadow queue; a block first
+//             compacts the hits of its queue entries, so a missed ray takes no lane
 //   connect   any-hit traversal of the shadow queue (:716-743); unoccluded -> accum += contrib
 //   finish    once fewer than kTailRays paths are alive, one launch runs every remaining path
 //             to completion (trace -> shade -> shadow per thread): the long glass-path tail
@@ -572,8 +573,68 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
             }
         ebase = (uint32_t)shard * Q.seg_cap;
     }
-    for (uint32_t base = beg; base < end; base += stride) {
+    // Unsorted: a missed ray ends its path and adds nothing (:321-322), so it gets no lane of a shading
+    // pass.  The block walks its batches of kBlock queue entries in order, reads each entry's hit
+    // record and compacts the hits (entry index and record, by ballot and a prefix over the waves)
+    // into an LDS ring; it shades once kBlock hits wait, or what is left after its last batch.  The
+    // hits keep the queue's order, so the rays and shadow rays appended stay grouped as before.
+    // A fill adds at most kBlock to fewer than kBlock waiting: the ring holds 2 * kBlock.
+    constexpr uint32_t kRing = 2 * kBlock;
+    __shared__ uint32_t ring_e[SORTED ? 1 : kRing];
+    __shared__ float4 ring_h[SORTED ? 1 : kRing];
+    __shared__ uint32_t ring_w[2][kBlock / 64];   // the waves' hit counts of a fill (double-buffered: one barrier per fill)
+    uint32_t head = 0, pending = 0, fills = 0;    // block-uniform
+    uint32_t base = beg;
+    while (true) {
         uint32_t g = base + threadIdx.x;
+        bool valid;
+        uint32_t slot = 0;
+        if (SORTED) {
+            if (base >= end) break;
+            valid = g < end;
+            base += stride;
+        } else {
+            while (pending < (uint32_t)kBlock && base < end) {
+                g = base + threadIdx.x;
+                uint32_t e = 0;
+                float4 hv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                bool hit = false;
+                if (g < end) {
+                    e = ebase + seg_pos(g, lk, Q.seg_cap);
+                    hv = ld_stream(&Q.W.hits[e]);
+                    hit = __float_as_uint(hv.y) != 0xffffffffu;
+                }
+                const unsigned long long m = __ballot(hit);
+                uint32_t* const w = ring_w[fills & 1u];
+                const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+                if (lane_id() == 0) w[wave] = (uint32_t)__popcll(m);
+                __syncthreads();
+                uint32_t off = 0, tot = 0;
+                #pragma unroll
+                for (uint32_t j = 0; j < (uint32_t)(kBlock / 64); ++j) {
+                    const uint32_t c = w[j];
+                    off += j < wave ? c : 0u;
+                    tot += c;
+                }
+                if (hit) {
+                    const uint32_t s = (head + pending + off + mbcnt64(m)) & (kRing - 1u);
+                    ring_e[s] = e;
+                    ring_h[s] = hv;
+                }
+                pending += __builtin_amdgcn_readfirstlane(tot);   // the same in every thread: the loops stay uniform
+                ++fills;
+                base += stride;
+            }
+            if (pending == 0u) break;
+            // the ring's new entries are written; the slots read below are free for the next fill
+            // once every thread has passed block_alloc3_oct's barriers
+            __syncthreads();
+            const uint32_t n = min(pending, (uint32_t)kBlock);
+            valid = threadIdx.x < n;
+            slot = (head + threadIdx.x) & (kRing - 1u);
+            head = (head + n) & (kRing - 1u);
+            pending -= n;
+        }
         StepResult r;
         r.next = false;
         r.shadow = false;
@@ -581,7 +642,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
         bool front = true;              // the continuation goes to the queue front (likely_long)
         f3 rayO = mk3(0, 0, 0), rayD = mk3(0, 0, 0);
         float4 ncol = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (g < end) {
+        if (valid) {
             float4 o, d, hv;
             size_t ce = 0;   // the entry's colour: sorted[4g + 3] / qc[cur][e]
             if (SORTED) {
@@ -590,10 +651,10 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
                 hv = Q.W.sorted[4 * (size_t)g + 2];
                 ce = 4 * (size_t)g + 3;
             } else {
-                const uint32_t e = ebase + seg_pos(g, lk, Q.seg_cap);
+                const uint32_t e = ring_e[slot];
+                hv = ring_h[slot];
                 o = ld_stream(&qin[2 * (size_t)e]);
                 d = ld_stream(&qin[2 * (size_t)e + 1]);
-                hv = ld_stream(&Q.W.hits[e]);
                 ce = e;
             }
             pid = __float_as_uint(o.w);
@@ -602,7 +663,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
             h.id = __float_as_uint(hv.y);
             h.u = hv.z;
             h.v = hv.w;
-            if (h.id != 0xffffffffu) {                                           // miss -> path ends (:321-322)
+            if (!SORTED || h.id != 0xffffffffu) {   // sorted: dropped by the sort already; unsorted: never in the ring
                 const uint32_t state = __float_as_uint(d.w);
                 const float4 c = state == 0u ? make_float4(1.0f, 1.0f, 1.0f, 0.0f)
                                              : (SORTED ? Q.W.sorted[ce] : ld_stream(&Q.W.qc[cur][ce]));
