@@ -9,7 +9,7 @@
 namespace rt {
 
 // The wavefront kernels' scheduling parameters, resolved (rt_tuning in rt_api.h: 0 = default there;
-// rt_api.cpp fills these in).  Per context: the library reads no environment variable for them.
+// rt_set_tuning in rt_api.cpp fills these in).  Per context: the library reads no environment variable for them.
 struct WfTuning {
     uint32_t tail = 4194304;      // finish threshold one frame at a time (frames in flight: kTailInFlight)
     int refill_min = 8;           // a wave refills once this many of its lanes are idle

@@ -1,4 +1,4 @@
-"""Edge cases of frames in flight (rt_api.cpp FrameSlot rotation): a resize between frames in
+"""Edge cases of frames in flight (rt_frame_ring.h, rt_api_frame.cpp): a resize between frames in
 flight, switching to a caller's stream mid-sequence (one slot from then on), a rank that owns no
 tiles, re-uploading the scene, and the on-device BVH rebuild between in-flight frames.  Each
 sequence must give the same bytes as one-frame-at-a-time rendering."""
