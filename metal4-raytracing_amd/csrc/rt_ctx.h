@@ -12,6 +12,7 @@
 #include "rt_bvh.h"
 #include "rt_frame_ring.h"
 #include "rt_kernels.h"
+#include "rt_wavefront.h"
 #include "rt_resources.h"
 
 struct MeshInfo {

@@ -244,6 +244,11 @@ __host__ __device__ __forceinline__ int highest_bit(uint32_t m) { return 31 - __
 __host__ __device__ __forceinline__ uint32_t pack_group(uint32_t base, bool flip, uint32_t hits) {
     return (base << 9) | ((uint32_t)flip << 8) | hits;
 }
+__host__ __device__ __forceinline__ void unpack_group(uint32_t e, uint32_t& base, bool& flip, uint32_t& hits) {
+    base = e >> 9;
+    flip = (e >> 8) & 1u;
+    hits = e & 0xffu;
+}
 
 // Closest-hit (ANY=false) / any-hit (ANY=true) traversal of the 8-wide BVH. Triangles found by a
 // node test are intersected before the next node is fetched (they shrink `best` first).
@@ -280,9 +285,7 @@ __host__ __device__ __forceinline__ bool trace8(const DevScene& S, f3 o, f3 d, f
             if (sp == 0) break;
             --sp;
             const uint32_t e = (uint32_t)stack[sp * kBlock];
-            g_base = e >> 9;
-            g_flip = (e >> 8) & 1u;
-            g_hits = e & 0xffu;
+            unpack_group(e, g_base, g_flip, g_hits);
         }
         const int r = g_flip ? highest_bit(g_hits) : lowest_bit(g_hits);
         g_hits &= ~(1u << r);

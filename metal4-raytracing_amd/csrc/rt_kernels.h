@@ -1,11 +1,11 @@
-// rt_kernels.h — kernel parameter blocks and launch entry points (device code lives in *.hip).
+// rt_kernels.h — FrameParams, the statistics flush and the launch entry points of the megakernel, the
+// on-device BVH build and the utility kernels (device code lives in *.hip; the wavefront pipeline: rt_wavefront.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "rt_device.h"
-#include "rt_wf_schedule.h"
 
 namespace rt {
 
@@ -76,138 +76,6 @@ __device__ __forceinline__ void block_flush_counters(unsigned long long* counter
 }
 
 void launch_megakernel(const DevScene& S, const FrameParams& P, int nblocks, bool count, hipStream_t stream);
-
-// Wavefront pipeline (rt_wavefront.hip): path state SoA indexed by path id
-// (own pixel index * spp + sample; extra samples after base_paths), ray queues of
-// {float4 o (w = path id), float4 d}, hit records {t, tri id, u, v}, shadow queue of
-// {float4 o (w = path id), float4 d (w = tmax), float4 contribution}.
-constexpr int kShards = 8;        // queue segments (one allocation counter each)
-// Counter slots: [0..7] queue 0, [8..15] queue 1, [16..23] shadow, [24] extra allocator,
-// [32..39] / [40..47] per-XCD chunk counters of the extend / connect launches; each slot on a
-// 128-B line of its own (cslot), so the per-XCD shards never contend for one line's atomics.
-constexpr int kCntStride = 32;
-constexpr int kCntSlotsWf = 74;                       // counter slots (cslot) before the diagnostics words
-constexpr int kWfDiagHist = kCntSlotsWf * kCntStride; // 64 words: wf_finish wave end-time histogram (50 us bins)
-constexpr int kWfDiagSteps = kWfDiagHist + 64;        // 66 words: wf_trace steps-per-ray histograms + max
-constexpr int kWfStat = kWfDiagSteps + 66;              // 3 words: rounds, wf_trace launches, their rays
-constexpr int kStatRounds = 0, kStatTraceLaunches = 1, kStatTraceRays = 2, kStatExtendRays = 3, kStatFinish = 4;
-// wf_finish_step diagnostics (RT_WF_LOG): summed over waves, s_memrealtime ticks (10 ns) spent in
-// shading passes and in total, shading passes and lanes shaded
-constexpr int kStatDiagShadeT = 5, kStatDiagTotalT = 6, kStatDiagPasses = 7, kStatDiagShaded = 8;
-// ... and split at the wave's queue exhaustion: iterations and ticks before / after it, and the
-// wave's active lanes summed over its iterations after it
-constexpr int kStatDiagItPre = 9, kStatDiagItPost = 10, kStatDiagTPre = 11, kStatDiagTPost = 12, kStatDiagLanesPost = 13;
-constexpr int kWfStatWords = 14;
-// wf_finish_step diagnostics (RT_WF_LOG): paths by segments run in the finish (32 bins) per entry
-// class (18: bounce 0..8 at entry, x refracting or not), then the waves' queue-exhaustion times
-// (64 bins of 50 us)
-constexpr int kWfDiagLen = kWfStat + kWfStatWords;
-constexpr int kWfDiagExh = kWfDiagLen + 18 * 32;
-constexpr int kWfCountWords = kCntSlotsWf * kCntStride + 64 + 66 + kWfStatWords + 18 * 32 + 64;
-__host__ __device__ constexpr uint32_t cslot(int c) { return (uint32_t)c * kCntStride; }
-struct WavefrontBuffers {
-    size_t queue_entries = 0;     // kShards segments of queue_entries / kShards
-    float4* p_accum = nullptr;
-    uint4* p_meta = nullptr;      // extra-sample paths only: (pixel, sample, 0, halton index)
-    // ray queues: entry e = {origin, w = path id}, {direction, w = path state bits: bounce | tpass << 8 |
-    // step << 16}; qc[q][e] = the path's throughput colour (absent for state 0, the primary ray: 1)
-    float4* q[2] = {nullptr, nullptr};
-    float4* qc[2] = {nullptr, nullptr};
-    float4* hits = nullptr;
-    float4* sq = nullptr;
-    uint32_t* counts = nullptr;   // device counter slots (see cslot)
-    uint32_t* h_counts = nullptr; // pinned host mirror
-    // device-clock launch spans (kTsSlots launch slots x kTsStride words, s_memrealtime) + pinned mirror
-    unsigned long long* tstamp = nullptr;
-    unsigned long long* h_tstamp = nullptr;
-    uint2* px_extra = nullptr;    // per own pixel: (first extra path - base_paths, count)
-    // per-bounce hit sort (wf_sort_*): the hits reordered by key as {o, d, hit, colour} float4 quads,
-    // per-(bin, block) counts, per-bin totals
-    float4* sorted = nullptr;
-    uint32_t* sort_table = nullptr;
-    uint32_t* sort_total = nullptr;
-    size_t cap_paths = 0;         // base + extra paths
-    size_t cap_pixels = 0;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    // FrameParams of the frame in flight: one device copy the kernels read, uploaded from a ring
-    // of pinned host slots
-    static constexpr int kParamSlots = 4;
-    FrameParams* d_params = nullptr;
-    FrameParams* h_params = nullptr;
-    hipEvent_t param_ev[kParamSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int param_slot = 0;
-};
-// Hit sort: kSortBlocks blocks of kSortThreads share one partition of the queue in the histogram
-// and scatter kernels; bins are a power of two in [kSortMinBins, kSortMaxBins].
-constexpr int kSortBlocks = 256;
-constexpr int kSortThreads = 1024;
-constexpr int kSortMinBins = 1024;
-constexpr int kSortMaxBins = 4096;
-constexpr int kSortBinsDefault = 0;   // off: measured slower on C3g (DESIGN.md §3 'Hit sort')
-// Per-frame measurements of the wavefront pipeline. stage_ms: [0] generate, [1] extend,
-// [2] shade, [3] connect, [4] resolve (+extra-sample bookkeeping), [5] finish, [6] hit sort.
-// Launch slots of the device-clock spans: per pass (base, extra samples) two per round (extend
-// 2k, connect 2k + 1; rounds <= 16) and the finish launch (kTsFinish); the extra pass at kTsPass.
-constexpr int kTsPass = 40, kTsFinish = 33, kTsSlots = 2 * kTsPass;
-// a launch slot: its start, then one end word per XCD, each on a 128-B line of its own (the last
-// wave of every block takes the max on its XCD's line; one line for all would serialise them)
-constexpr int kTsLine = 16, kTsStride = 9 * kTsLine;
-// the counter words and, 8-byte aligned after them, the launch spans share one allocation
-constexpr size_t kWfTsOffset = ((size_t)kWfCountWords * 4 + 7) / 8 * 8;
-constexpr size_t kWfCountAllocBytes = kWfTsOffset + (size_t)kTsSlots * kTsStride * 8;
-struct WfFrameStats {
-    float trace_dev_ms, finish_dev_ms;   // device-clock spans of the extend + connect / finish launches
-    int trace_dev_launches, finish_dev_launches;
-    float stage_ms[7];
-    int iterations;
-    unsigned long long trace_rays;  // rays traced by wf_trace launches (extend + connect)
-    unsigned long long trace_closest_rays;   // the extend share
-    int trace_launches;
-    float trace_ms;                 // their summed device time
-    int finish_launches;
-    int graph_mode;                 // kGraph*: how the frame was submitted
-};
-// Host-side record of a frame enqueued with device-side control: events between the launches and
-// which stage each interval belongs to; collected once the frame is done (wavefront_collect).
-struct WfTimeline {
-    static constexpr int kMaxEv = 160;
-    struct Span {
-        int stage, a, b;
-    };
-    hipEvent_t ev[kMaxEv] = {};
-    Span spans[kMaxEv];
-    int n_ev = 0, n_spans = 0;
-    bool pending = false;
-    bool dev_spans = false;   // the frame recorded device-clock launch spans (tstamp copied back)
-    // RT_GRAPH: the slot's frame captured as two HIP graphs (events recorded as external event
-    // nodes, so the spans above keep timing it) and replayed while `key` (every launch argument and
-    // enqueue decision of the frame) is unchanged: exec[0] up to the motion vectors, exec[1] the
-    // rest, with the wait for the previous frame enqueued between them (a plain stream wait, not a
-    // captured external-event wait node)
-    hipGraphExec_t exec[2] = {nullptr, nullptr};
-    std::vector<uint8_t> key;
-    bool graph_failed = false;   // capture was refused once: this slot stays eager
-    int graph_mode = 0;          // the pending frame: kGraph* (rt_stats total_graph_*)
-};
-constexpr int kGraphEager = 0, kGraphReplay = 1, kGraphCapture = 2, kGraphFallback = 3;
-// One wavefront frame of `own_tiles` tiles on `stream` (rt_wavefront_host.cpp); false on a HIP
-// error (*err).  Device-driven rounds, the default, enqueue the whole frame and return: `tl`
-// receives the timeline and wavefront_collect fills the stats once the stream has finished;
-// graphs: as two replayed HIP graphs.  Host-driven rounds (tu.host_ctl or tu.log set, no `tl`, or
-// a finish threshold <= 1) read the queue sizes back every round; *fs is complete on return.
-// sched: the finish threshold, grid shares and team drain (wf_schedule, rt_wf_schedule.h).
-// count: the traversal statistics counters; spans: device-clock launch spans.  sort_bins: hit-sort
-// bins (0 = no sort).  extra_pass: the motion-adaptive extra samples can be non-zero this frame
-// (something moved in this or the previous frame); device-driven rounds skip their pass otherwise.
-// prev_done (may be null): the previous frame, in flight on another stream; the extra-sample pass
-// and the resolve (which read its accumulation and motion outputs) are ordered after it,
-// everything before them overlaps it.
-bool run_wavefront(const DevScene& S, const FrameParams& P, WavefrontBuffers& W, const WfTuning& tu,
-                   const WfSchedule& sched, int own_tiles, bool count, bool spans, int sort_bins, bool extra_pass,
-                   hipStream_t stream, hipEvent_t prev_done, WfTimeline* tl, WfFrameStats* fs, const char** err,
-                   bool graphs = true);
-bool wavefront_collect(const WavefrontBuffers& W, WfTimeline& T, WfFrameStats* fs, const char** err);
-size_t wavefront_queue_entries(size_t paths, int max_extra);
 
 // Packed-tile layout of the multi-GPU gather: element i of a rank's packed buffer is pixel
 // (i % T, (i / T) % T) of its (i / T^2)-th own tile; own tile k is tile id rank + k * nranks.

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "rt_kernels.h"
+#include "rt_wavefront.h"   // kSortMaxBins: the resolution of tri_bin
 
 #include <cstring>
 #include <utility>

@@ -14,19 +14,17 @@
 //   [extra]   motion-adaptive extra samples (:779-789) as a second generate/iterate pass
 //   resolve   per pixel: sum samples in sample order, average, temporal EMA (:777, :792-819)
 //
-// Queues are split into kShards segments; a block appends to segment blockIdx % 8 with ONE
-// returning atomic per 256 entries (wave ballot + LDS prefix), so no counter word sees more
-// than ~1/2048 of the entries (one word serialises at ~88 atomics/us, MI355X_MICROARCH.md
-// 'dequeue').  Grids are multiples of 8, so segment k only receives chunks c == k (mod 8) and
-// a segment of n/8 + 4096 (+ 256 per extra sample) entries can never overflow.
-//
 // Results are bit-identical to the megakernel: per-path arithmetic is the same shade_step,
 // the accumulation order per path is the reference's (emission of step s, then its shadow
 // contribution, then step s+1), and samples are summed per pixel in sample order.
 //
-// This file holds the kernels only; rt_wavefront_host.cpp launches them, through wf_kernels() below.
+// This file holds the kernels only: the sharded queues and the index maths are rt_wf_queue.h, the
+// stepwise traversal rt_trav.h, the counter words rt_wf_counters.h; rt_wavefront_host.cpp launches
+// the kernels, through wf_kernels() below.
 #include "rt_shade.h"
+#include "rt_trav.h"
 #include "rt_wavefront.h"
+#include "rt_wf_queue.h"
 
 #include <array>
 #include <utility>
@@ -35,146 +33,6 @@ namespace rt {
 
 namespace {
 
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t mbcnt64(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-struct BlockAlloc {
-    uint32_t w[kBlock / 64];
-};
-
-// Block-aggregated slot allocation; every thread of the block calls it (converged loop).
-__device__ __forceinline__ uint32_t block_alloc(bool pred, uint32_t* counter, BlockAlloc& sh) {
-    const int wave = threadIdx.x >> 6;
-    unsigned long long m = __ballot(pred);
-    uint32_t prefix = mbcnt64(m);
-    if (lane_id() == 0) sh.w[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t c0 = sh.w[0], c1 = sh.w[1], c2 = sh.w[2], c3 = sh.w[3];
-        uint32_t tot = c0 + c1 + c2 + c3;
-        uint32_t b = tot ? atomicAdd(counter, tot) : 0u;
-        sh.w[0] = b;
-        sh.w[1] = b + c0;
-        sh.w[2] = b + c0 + c1;
-        sh.w[3] = b + c0 + c1 + c2;
-    }
-    __syncthreads();
-    uint32_t r = sh.w[wave] + prefix;
-    __syncthreads();
-    return r;
-}
-
-// Three block-aggregated allocations at once (wf_shade: pr[0] shadow ray, pr[1] front / pr[2] back
-// continuation ray), one returning global atomic per part and block, with the continuation rays
-// grouped by the direction octant `oct` (3 bits) inside each part's range: a per-block counting
-// sort of the appends through LDS atomics (the rank inside an octant is arbitrary), no separate
-// sort pass.
-struct BlockAllocOct {
-    uint32_t cnt[3][8];    // shadow uses [0][0]
-    uint32_t base[3][8];
-};
-__device__ __forceinline__ void block_alloc3_oct(const bool (&pr)[3], uint32_t oct, uint32_t* const (&ctr)[3],
-                                                 BlockAllocOct& sh, uint32_t (&out)[3]) {
-    if (threadIdx.x < 24) (&sh.cnt[0][0])[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t rank[3] = {0u, 0u, 0u};
-    #pragma unroll
-    for (int i = 0; i < 3; ++i)
-        if (pr[i]) rank[i] = atomicAdd(&sh.cnt[i][i ? oct : 0u], 1u);
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int i = threadIdx.x;
-        uint32_t tot = 0, pre[8];
-        #pragma unroll
-        for (int o = 0; o < 8; ++o) { pre[o] = tot; tot += sh.cnt[i][o]; }
-        const uint32_t b = tot ? atomicAdd(ctr[i], tot) : 0u;
-        #pragma unroll
-        for (int o = 0; o < 8; ++o) sh.base[i][o] = b + pre[o];
-    }
-    __syncthreads();
-    #pragma unroll
-    for (int i = 0; i < 3; ++i) out[i] = sh.base[i][i ? oct : 0u] + rank[i];
-    __syncthreads();
-}
-
-// Block-aggregated allocation of v slots per thread (wave scan + LDS prefix, one atomic per block).
-__device__ __forceinline__ uint32_t block_alloc_n(uint32_t v, uint32_t* counter, BlockAlloc& sh) {
-    const int wave = threadIdx.x >> 6;
-    const uint32_t lane = lane_id();
-    uint32_t incl = v;
-    #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t t = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += t;
-    }
-    if (lane == 63) sh.w[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t c0 = sh.w[0], c1 = sh.w[1], c2 = sh.w[2], c3 = sh.w[3];
-        uint32_t tot = c0 + c1 + c2 + c3;
-        uint32_t b = tot ? atomicAdd(counter, tot) : 0u;
-        sh.w[0] = b;
-        sh.w[1] = b + c0;
-        sh.w[2] = b + c0 + c1;
-        sh.w[3] = b + c0 + c1 + c2;
-    }
-    __syncthreads();
-    uint32_t r = sh.w[wave] + incl - v;
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const uint32_t lane = lane_id();
-    #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(v, off, 64);
-        if (lane >= (uint32_t)off) v += t;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t compact1by1(uint32_t x) {
-    x &= 0x55555555u;
-    x = (x | (x >> 1)) & 0x33333333u;
-    x = (x | (x >> 2)) & 0x0f0f0f0fu;
-    x = (x | (x >> 4)) & 0x00ff00ffu;
-    x = (x | (x >> 8)) & 0x0000ffffu;
-    return x;
-}
-
-
-__device__ __forceinline__ uint32_t pack_state(int bounce, int tpass, int step) {
-    return (uint32_t)bounce | ((uint32_t)tpass << 8) | ((uint32_t)step << 16);
-}
-
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {   // n / f.d (make_fastdiv)
-    const uint32_t t = __umulhi(f.m, n);
-    return (t + ((n - t) >> f.s1)) >> f.s2;
-}
-
-// own pixel index -> image coordinates (tiles tile_id % nranks == rank, Morton order in a tile)
-__device__ __forceinline__ void own_pixel(const WfParams& Q, uint32_t i, int& px, int& py) {
-    const uint32_t T = (uint32_t)Q.tile;
-    const uint32_t k = fdiv(i, Q.tile_px_div), r = i - k * Q.tile_px_div.d;
-    const uint32_t tid = (uint32_t)Q.rank + k * (uint32_t)Q.nranks;
-    const uint32_t ty = fdiv(tid, Q.tiles_x_div), tx = tid - ty * Q.tiles_x_div.d;
-    uint32_t lx, ly;
-    if ((T & (T - 1)) == 0) {
-        lx = compact1by1(r);
-        ly = compact1by1(r >> 1);
-    } else {
-        lx = r % T;
-        ly = r / T;
-    }
-    px = (int)(tx * T + lx);
-    py = (int)(ty * T + ly);
-}
-
-// counter slots only the kernels use (the others: rt_wavefront.h)
-constexpr int kCntSorted = 26;                 // hits the sort kept (misses dropped) = shade's input size
 constexpr uint32_t kNoKey = 0xffffffffu;       // sort key of a miss (dropped by the sort)
 
 // Device-clock span of a launch (WfFrameStats::trace_dev_ms): block 0 records the start, the last
@@ -189,7 +47,7 @@ __device__ __forceinline__ void ts_start(const WfParams& Q, int ts) {
 __device__ __forceinline__ void ts_end(const WfParams& Q, int ts, uint32_t* done) {
     if (ts < 0 || lane_id() != 0) return;
     if (atomicAdd(done, 1u) == (blockDim.x + 63u) / 64u - 1u)
-        atomicMax(&Q.W.tstamp[ts * kTsStride + kTsLine * (1 + (int)(blockIdx.x % 8u))],
+        atomicMax(&Q.W.tstamp[ts * kTsStride + kTsLine * (1 + (int)(blockIdx.x % (uint32_t)kTsXcds))],
                   (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
 
@@ -201,68 +59,6 @@ __device__ __forceinline__ bool tail_mode(const WfParams& Q) {
     return Q.dev_ctl && __builtin_amdgcn_readfirstlane(Q.W.counts[cslot(kCntTailMode)]) != 0u;
 }
 
-// Inclusive prefix of a sharded queue's segment counts, loaded once per kernel (uniform, so the
-// loads are scalar and the lookups below stay in registers).
-struct ShardPrefix {
-    uint32_t end[kShards];
-};
-__device__ __forceinline__ ShardPrefix load_prefix(const uint32_t* cnt, uint32_t cap = 0xffffffffu) {
-    ShardPrefix p;
-    uint32_t acc = 0;
-    #pragma unroll
-    for (int k = 0; k < kShards; ++k) {
-        acc += min(__builtin_amdgcn_readfirstlane(cnt[cslot(k)]), cap);   // a counter may run past a full segment
-        p.end[k] = acc;
-    }
-    return p;
-}
-// A ray queue's shard k holds L[k] entries at the front of its segment (ascending) and S[k] at the
-// back (descending from seg_cap - 1): wf_shade appends the continuation rays of paths that have
-// refracted (likely_long) at the front and the rest at the back, so the finish kernel, which
-// takes the queue front parts first, starts the long glass paths before the short ones (they
-// would otherwise set the end of its launch).  Primary rays (generate, extra samples) go to the
-// front.  Counters: L in [q * 8 + k], S in [kCntBack + q * 8 + k].
-struct QueueShards {
-    uint32_t L[kShards], S[kShards];
-};
-__device__ __forceinline__ QueueShards load_queue(const uint32_t* counts, int q, uint32_t seg_cap) {
-    QueueShards r;
-    #pragma unroll
-    for (int k = 0; k < kShards; ++k) {
-        const uint32_t l = min(__builtin_amdgcn_readfirstlane(counts[cslot(q * kShards + k)]), seg_cap);
-        r.L[k] = l;
-        r.S[k] = min(__builtin_amdgcn_readfirstlane(counts[cslot(kCntBack + q * kShards + k)]), seg_cap - l);
-    }
-    return r;
-}
-__device__ __forceinline__ uint32_t queue_len(const QueueShards& qs) {
-    uint32_t n = 0;
-    #pragma unroll
-    for (int k = 0; k < kShards; ++k) n += qs.L[k] + qs.S[k];
-    return n;
-}
-// shard-local index g (< L + S) -> position in the shard's segment
-__device__ __forceinline__ uint32_t seg_pos(uint32_t g, uint32_t l, uint32_t seg_cap) {
-    return g < l ? g : seg_cap - 1u - (g - l);
-}
-// dense consumer index g (< queue_len) -> entry index: the front parts of all shards first, then the back parts
-__device__ __forceinline__ uint32_t dense_entry(const QueueShards& qs, uint32_t g, uint32_t seg_cap) {
-    uint32_t ltot = 0;
-    #pragma unroll
-    for (int k = 0; k < kShards; ++k) ltot += qs.L[k];
-    const bool back = g >= ltot;
-    if (back) g -= ltot;
-    uint32_t k = 0, start = 0, acc = 0;
-    #pragma unroll
-    for (int j = 0; j < kShards - 1; ++j) {
-        acc += back ? qs.S[j] : qs.L[j];
-        const bool past = g >= acc;
-        k = past ? (uint32_t)(j + 1) : k;
-        start = past ? acc : start;
-    }
-    const uint32_t i = g - start;
-    return k * seg_cap + (back ? seg_cap - 1u - i : i);
-}
 __device__ __forceinline__ bool likely_long(const PathRegs& p) {
     return p.tpass > 0 || p.bounce < p.step;
 }
@@ -300,140 +96,6 @@ __device__ __forceinline__ void write_pixel_outputs(const FrameParams& P, uint32
 
 }  // namespace
 
-// ---- one traversal step of the compressed 8-wide BVH, shared by wf_trace and wf_finish_step ------
-// The state of one query in registers: ray setup, closest hit so far (u = bu / bdet, v = bv / bdet:
-// the division happens once, when the query ends), the current node group (child base, flip,
-// remaining internal hits), the pending triangles of the last node test, and the LDS stack.
-struct Trav {
-    RaySetup R;
-    float best, bu, bv, bdet;
-    uint32_t best_id, g_base, g_hits, t_base, t_mask, t_valid;
-    bool g_flip, hit_any;
-    int sp;
-};
-
-__device__ __forceinline__ void trav_start(Trav& T, f3 o, f3 d, float tmax) {
-    T.R = ray_setup(o, d);
-    T.best = tmax;
-    T.best_id = 0xffffffffu;
-    T.bu = T.bv = 0.0f;
-    T.bdet = 1.0f;
-    T.g_base = 0;
-    T.g_hits = 1;   // virtual group holding the root
-    T.g_flip = false;
-    T.t_mask = 0;
-    T.sp = 0;
-    T.hit_any = false;
-}
-
-// One iteration of a query: up to two triangles of the last node test (both fetched before either
-// is tested: one memory latency; tested in mask order, so closest-hit updates are those of the
-// serial loop), then — for a lane whose triangles ran out in this step, and for every lane without
-// triangles — one 8-wide node: the next hit child of the current group in slot order (the node's
-// children sorted along its longest axis, reversed for rays going the other way), its five 16-B
-// words fetched from global memory (an LDS copy of the top levels measured no faster, DESIGN.md
-// §3.5).  Returns true once the query is finished (any-hit: an occluder was found).
-// The next node's group / stack bookkeeping and index (the step after the triangles of the last
-// node test, or a node step without triangles).
-__device__ __forceinline__ uint32_t next_node(Trav& T, int* stack, bool& overflow) {
-    if (!T.g_hits) {
-        --T.sp;
-        const uint32_t ent = (uint32_t)stack[T.sp * kBlock];
-        T.g_base = ent >> 9;
-        T.g_flip = (ent >> 8) & 1u;
-        T.g_hits = ent & 0xffu;
-    }
-    const int r = T.g_flip ? highest_bit(T.g_hits) : lowest_bit(T.g_hits);
-    T.g_hits &= ~(1u << r);
-    if (T.g_hits) {
-        if (T.sp < kStackSize) {
-            stack[T.sp * kBlock] = (int)pack_group(T.g_base, T.g_flip, T.g_hits);
-            ++T.sp;
-        } else {
-            overflow = true;
-        }
-    }
-    return T.g_base + (uint32_t)r;
-}
-
-// The node half of a traversal step: the next node of the current group (or the stack), its five
-// 16-B words from global memory, the 8-wide test.
-template <bool COUNT>
-__device__ __forceinline__ void node_step(const DevScene& S, Trav& T, int* stack, TraceCounters& tc, bool& overflow,
-                                          float cull) {
-    const uint32_t ni = next_node(T, stack, overflow);
-    if (COUNT) tc.nodes++;
-    const NodeWords w = load_node8(S.nodes8, ni);
-    test_node8_words(w, T.R, 0.0f, fminf(cull, T.best), T.g_hits, T.t_mask, T.t_valid, T.g_base, T.t_base, T.g_flip);
-}
-
-// `cull`: the distance bound of the box and triangle tests together with T.best (the lower of the
-// two); lower than T.best in the finish kernel's team drain (the closest hit any member of the team
-// has found), where T.best stays this lane's own hit.
-template <bool COUNT>
-__device__ __forceinline__ bool trav_step(const DevScene& S, Trav& T, bool any, int* stack, TraceCounters& tc,
-                                          bool& overflow, float cull) {
-    bool tdone = false;
-    if (T.t_mask != 0u) {
-        const int k0 = lowest_bit(T.t_mask);
-        T.t_mask &= T.t_mask - 1u;
-        const bool two = T.t_mask != 0u;
-        const int k1 = two ? lowest_bit(T.t_mask) : k0;
-        if (two) T.t_mask &= T.t_mask - 1u;
-        // the bound is re-read for every test: a triangle must not be accepted beyond a closer hit
-        // found earlier in this step (the update below assumes t <= T.best)
-#ifdef RT_XP_STALE_BOUND
-        // round 3's bug, kept as a build-time switch to show the parity tests catch it
-        // (tests/test_gpu_traversal_variants.py): both triangles against the bound from before the step
-        const float stale_bound = fminf(cull, T.best);
-#define RT_ISECT(a, b, c) intersect_rot(T.R.pre, T.R.o, a, b, c, 0.0f, stale_bound, &t, &u, &v, &dt)
-#else
-#define RT_ISECT(a, b, c) intersect_rot(T.R.pre, T.R.o, a, b, c, 0.0f, fminf(cull, T.best), &t, &u, &v, &dt)
-#endif
-        // each vertex as the ray's (kz, kx, ky) window of its record: three 12-B loads and the id
-        // per triangle, all in the slot's 64-B line (rt_device.h); both triangles' loads issue
-        // before either test
-        const uint32_t kz = (uint32_t)T.R.pre.kz;
-        const uint32_t f0 = tri_slot(T.t_base, T.t_valid, k0) * (uint32_t)kTriFloats + kz;
-        const uint32_t f1 = tri_slot(T.t_base, T.t_valid, k1) * (uint32_t)kTriFloats + kz;
-        const f3 a0 = tri_window_at(S.tris, f0), a1 = tri_window_at(S.tris, f0 + 5u), a2 = tri_window_at(S.tris, f0 + 10u);
-        const uint32_t ida = tri_id_at(S.tris, f0 - kz);
-        const f3 b0 = tri_window_at(S.tris, f1), b1 = tri_window_at(S.tris, f1 + 5u), b2 = tri_window_at(S.tris, f1 + 10u);   // = a for one triangle
-        const uint32_t idb = tri_id_at(S.tris, f1 - kz);
-        if (COUNT) tc.tris += two ? 2u : 1u;
-        float t, u, v, dt;
-        if (RT_ISECT(a0, a1, a2)) {
-            const uint32_t id = ida;
-            if (any) {
-                T.hit_any = true;
-                tdone = true;
-            } else if (t < T.best || id < T.best_id) {
-                T.best = t;
-                T.best_id = id;
-                T.bu = u;
-                T.bdet = dt;
-                T.bv = v;
-            }
-        }
-        if (two && !tdone && RT_ISECT(b0, b1, b2)) {
-            const uint32_t id = idb;
-            if (any) {
-                T.hit_any = true;
-                tdone = true;
-            } else if (t < T.best || id < T.best_id) {
-                T.best = t;
-                T.best_id = id;
-                T.bu = u;
-                T.bdet = dt;
-                T.bv = v;
-            }
-        }
-    }
-    if (!tdone && T.t_mask == 0u && (T.g_hits != 0u || T.sp > 0)) node_step<COUNT>(S, T, stack, tc, overflow, cull);
-    return tdone || (T.t_mask == 0u && T.g_hits == 0u && T.sp == 0);
-#undef RT_ISECT
-}
-
 // ---- base paths ----------------------------------------------------------------------------------------
 // Halton index of sample s of pixel pix in this frame (:263-270)
 __device__ __forceinline__ uint32_t base_hidx(const FrameParams& P, int spp, uint32_t pix, int s) {
@@ -447,10 +109,10 @@ __device__ __forceinline__ uint32_t base_hidx(const FrameParams& P, int spp, uin
 __device__ __forceinline__ bool base_path(const FrameParams& P, const WfParams& Q, const ShadeTabs& halton, uint32_t pid,
                                           uint32_t& pix, int& s, uint32_t& hidx, f3& o, f3& d) {
     const Uniforms& U = P.U;
-    const uint32_t i = fdiv(pid, Q.spp_div);
-    s = (int)(pid - i * Q.spp_div.d);
+    const uint32_t i = fdiv(pid, Q.px.spp_div);
+    s = (int)(pid - i * Q.px.spp_div.d);
     int px, py;
-    own_pixel(Q, i, px, py);
+    own_pixel(Q.px, i, px, py);
     if (px >= U.width || py >= U.height) return false;
     pix = (uint32_t)py * (uint32_t)U.width + (uint32_t)px;
     hidx = base_hidx(P, Q.spp, pix, s);
@@ -464,12 +126,37 @@ __device__ __forceinline__ uint3 path_meta(const FrameParams& P, const WfParams&
         const uint4 m = Q.W.p_meta[pid];
         return make_uint3(m.x, m.y, m.w);
     }
-    const uint32_t i = fdiv(pid, Q.spp_div);
-    const int s = (int)(pid - i * Q.spp_div.d);
+    const uint32_t i = fdiv(pid, Q.px.spp_div);
+    const int s = (int)(pid - i * Q.px.spp_div.d);
     int px, py;
-    own_pixel(Q, i, px, py);
+    own_pixel(Q.px, i, px, py);
     const uint32_t pix = (uint32_t)py * (uint32_t)P.U.width + (uint32_t)px;
     return make_uint3(pix, (uint32_t)s, base_hidx(P, Q.spp, pix, s));
+}
+// Queue entry {o, d} -> the path it carries: its id (o.w), its (pixel, sample, state bits, Halton
+// index) and its registers.  colour(): the entry's throughput colour, read only past state 0 (the
+// primary ray's is 1).  A continuation ray past bounce 0 carries its Halton index in the colour's w:
+// the pixel and sample (and the per-pixel random offset behind them) are read only at bounce 0
+// (:342-389).  read_accum: start from the stored accumulator, else from zero.
+template <typename Colour>
+__device__ __forceinline__ void load_path(const FrameParams& P, const WfParams& Q, const float4& o, const float4& d,
+                                          Colour colour, bool read_accum, uint32_t& pid, uint4& meta, PathRegs& p) {
+    pid = __float_as_uint(o.w);
+    const uint32_t state = __float_as_uint(d.w);
+    const float4 c = state == 0u ? make_float4(1.0f, 1.0f, 1.0f, 0.0f) : colour();
+    const PathState st = unpack_state(state);
+    if (st.bounce != 0) {
+        meta = make_uint4(0u, 1u, state, __float_as_uint(c.w));
+    } else {
+        const uint3 pm = path_meta(P, Q, pid);
+        meta = make_uint4(pm.x, pm.y, state, pm.z);
+    }
+    const float4 a = read_accum ? Q.W.p_accum[pid] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    p.color = mk3(c.x, c.y, c.z);
+    p.accum = mk3(a.x, a.y, a.z);
+    p.bounce = st.bounce;
+    p.tpass = st.tpass;
+    p.step = st.step;
 }
 // Per-pixel defaults, written by the pixel's sample-0 path (:252-261).
 __device__ __forceinline__ void init_pixel(const FrameParams& P, uint32_t pix) {
@@ -527,14 +214,6 @@ __global__ void __launch_bounds__(kBlock) wf_generate(DevScene S, const FramePar
 // blocks of XCD k (blockIdx % 8) shade the k-th eighth of it, so one XCD's L2 serves one scene
 // region and the rays / shadow rays it appends to its queue shard stay grouped by region for
 // the next extend / connect launches (which hand shard k's range to XCD k).
-// a 16-B load of data read once (nontemporal: it does not displace the lines gathered beside it).
-// wf_shade and the finish refill read their queue entries this way; wf_trace (extend) does not
-// (wf_shade reads the same entries again: nontemporal extend loads slowed it, round 4)
-__device__ __forceinline__ float4 ld_stream(const float4* p) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
 template <bool FULL, bool SORTED>
 __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur) {
     const FrameParams& P = *Pp;   // per-frame parameters in device memory
@@ -605,17 +284,8 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
                     hit = __float_as_uint(hv.y) != 0xffffffffu;
                 }
                 const unsigned long long m = __ballot(hit);
-                uint32_t* const w = ring_w[fills & 1u];
-                const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-                if (lane_id() == 0) w[wave] = (uint32_t)__popcll(m);
-                __syncthreads();
-                uint32_t off = 0, tot = 0;
-                #pragma unroll
-                for (uint32_t j = 0; j < (uint32_t)(kBlock / 64); ++j) {
-                    const uint32_t c = w[j];
-                    off += j < wave ? c : 0u;
-                    tot += c;
-                }
+                uint32_t off, tot;
+                block_prefix<kBlock / 64>(lane_id() == 0, (uint32_t)__popcll(m), ring_w[fills & 1u], off, tot);
                 if (hit) {
                     const uint32_t s = (head + pending + off + mbcnt64(m)) & (kRing - 1u);
                     ring_e[s] = e;
@@ -657,36 +327,22 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
                 d = ld_stream(&qin[2 * (size_t)e + 1]);
                 ce = e;
             }
-            pid = __float_as_uint(o.w);
             Hit h;
             h.t = hv.x;
             h.id = __float_as_uint(hv.y);
             h.u = hv.z;
             h.v = hv.w;
+            pid = __float_as_uint(o.w);
             if (!SORTED || h.id != 0xffffffffu) {   // sorted: dropped by the sort already; unsorted: never in the ring
-                const uint32_t state = __float_as_uint(d.w);
-                const float4 c = state == 0u ? make_float4(1.0f, 1.0f, 1.0f, 0.0f)
-                                             : (SORTED ? Q.W.sorted[ce] : ld_stream(&Q.W.qc[cur][ce]));
-                // a continuation ray past bounce 0 carries its Halton index in qc.w: the pixel and sample
-                // (and the per-pixel random offset behind them) are read only at bounce 0 (:342-389)
-                uint4 meta;
-                if ((state & 0xffu) != 0u) {
-                    meta = make_uint4(0u, 1u, state, __float_as_uint(c.w));
-                } else {
-                    const uint3 pm = path_meta(P, Q, pid);
-                    meta = make_uint4(pm.x, pm.y, state, pm.z);
-                }
                 // FULL=false: shade_step only adds color * emission to accum (:585), so it runs on a
                 // zero accumulator and the stored one is read and updated only when that term is
                 // non-zero (accum is never -0, so a + (0 + x) == a + x bit for bit); FULL (debug
                 // modes assign accum) reads it first
-                float4 a = FULL ? Q.W.p_accum[pid] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                uint4 meta;
                 PathRegs p;
-                p.color = mk3(c.x, c.y, c.z);
-                p.accum = mk3(a.x, a.y, a.z);
-                p.bounce = (int)(meta.z & 0xffu);
-                p.tpass = (int)((meta.z >> 8) & 0xffu);
-                p.step = (int)(meta.z >> 16);
+                load_path(P, Q, o, d, [&]() { return SORTED ? Q.W.sorted[ce] : ld_stream(&Q.W.qc[cur][ce]); }, FULL, pid,
+                          meta, p);
+                const f3 a = p.accum;
                 int sample = (int)meta.y;
                 rayO = ld3(o);
                 rayD = ld3(d);
@@ -771,13 +427,10 @@ __global__ void __launch_bounds__(kSortBlocks) wf_sort_rowscan(WfParams Q) {
     uint32_t* row = Q.W.sort_table + (size_t)blockIdx.x * kSortBlocks;
     const uint32_t v = row[threadIdx.x];
     const uint32_t incl = wave_incl_scan(v);
-    const int wave = threadIdx.x >> 6;
-    if (lane_id() == 63) w[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int i = 0; i < wave; ++i) base += w[i];
+    uint32_t base, total;
+    block_prefix<kSortBlocks / 64>(lane_id() == 63, incl, w, base, total);
     row[threadIdx.x] = base + incl - v;
-    if (threadIdx.x == kSortBlocks - 1) Q.W.sort_total[blockIdx.x] = base + incl;
+    if (threadIdx.x == kSortBlocks - 1) Q.W.sort_total[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(kSortThreads) wf_sort_scatter(DevScene S, WfParams Q, int cur) {
@@ -795,17 +448,14 @@ __global__ void __launch_bounds__(kSortThreads) wf_sort_scatter(DevScene S, WfPa
         s += Q.W.sort_total[threadIdx.x * per + i];
     }
     const uint32_t incl = wave_incl_scan(s);
-    const int wave = threadIdx.x >> 6;
-    if (lane_id() == 63) w[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int i = 0; i < wave; ++i) base += w[i];
+    uint32_t base, total;
+    block_prefix<kSortThreads / 64>(lane_id() == 63, incl, w, base, total);
     const uint32_t excl = base + incl - s;
     for (uint32_t i = 0; i < per; ++i) {
         const uint32_t k = threadIdx.x * per + i;
         off[k] = excl + loc[i] + Q.W.sort_table[(size_t)k * kSortBlocks + blockIdx.x];
     }
-    if (blockIdx.x == 0 && threadIdx.x == kSortThreads - 1) Q.W.counts[cslot(kCntSorted)] = excl + s;
+    if (blockIdx.x == 0 && threadIdx.x == kSortThreads - 1) Q.W.counts[cslot(kCntSorted)] = total;
     __syncthreads();
     const float4* qin = Q.W.q[cur];
     uint32_t beg, end;
@@ -974,8 +624,8 @@ wf_trace(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur, in
             if (trav_step<COUNT>(S, T, ANY, stack, tc, overflow, T.best)) {
                 active = false;
                 if (COUNT && Q.diag) {   // steps-per-ray histogram (log2 bins) of the counting frame
-                    atomicAdd(&Q.W.counts[kWfDiagSteps + (ANY ? 32 : 0) + (31 - __builtin_clz(steps))], 1u);
-                    atomicMax(&Q.W.counts[kWfDiagSteps + 64 + (ANY ? 1 : 0)], steps);
+                    atomicAdd(&Q.W.counts[kWfDiagSteps + (ANY ? kDiagStepBins : 0) + (31 - __builtin_clz(steps))], 1u);
+                    atomicMax(&Q.W.counts[kWfDiagSteps + 2 * kDiagStepBins + (ANY ? 1 : 0)], steps);
                 }
                 if (ANY) acc = !T.hit_any;
                 else Q.W.hits[e] = make_float4(T.best, __uint_as_float(T.best_id), T.bu / T.bdet, T.bv / T.bdet);
@@ -1003,8 +653,10 @@ wf_trace(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur, in
 // continues with its shadow ray, its next ray, or the next path of the queue.  A wave therefore
 // costs the sum of its own lanes' steps, not the sum over segments of its slowest lane's query:
 // the glass paths left at the tail (up to ~23 segments) do not wait for their wave's worst ray
-// every segment.  Four waves per SIMD: the shading code's register peak (119 VGPRs, no scratch);
-// five were measured no faster.
+// every segment.  Four waves per SIMD (a budget of 128 VGPRs, which the shading code's peak fills:
+// the radiance instances take 126-128 VGPRs and no scratch, 36 B when counting, the FULL ones
+// 160-196 B of scratch; profiles/r09_wavefront_split.txt); five were measured no faster (DESIGN.md
+// §3.5).
 template <bool COUNT, bool FULL, bool TEAM>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4)))
 wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur, int ts) {
@@ -1016,6 +668,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
     __shared__ float4 lds_inst[3 * kInstLds];
     __shared__ Light lds_light[kLightLds];
     __shared__ float lds_sray[6][kBlock];   // each lane's shadow ray (origin, direction)
+    __shared__ float lds_tx[4][kBlock];     // team drain: each leader's shadow tmax and contribution
     int* stack = &lds_stack[threadIdx.x];
     __shared__ uint32_t ts_done;
     if (threadIdx.x == 0) ts_done = 0u;
@@ -1062,8 +715,9 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
     auto end_path = [&]() {
         Q.W.p_accum[pid] = make_float4(p.accum.x, p.accum.y, p.accum.z, 0.0f);
         if (Q.diag > 1) {   // RT_WF_LOG=2: segments by entry class: bounce at entry, refracting (tpass > 0) or not
-            const uint32_t b0 = min(meta.z & 0xffu, 8u), tp0 = (meta.z >> 8) & 0xffu;
-            atomicAdd(&Q.W.counts[kWfDiagLen + ((tp0 ? 9u : 0u) + b0) * 32u + min(segs, 31u)], 1u);
+            const uint32_t b0 = min(meta.z & 0xffu, (uint32_t)kDiagLenBounces - 1u), tp0 = (meta.z >> 8) & 0xffu;
+            atomicAdd(&Q.W.counts[kWfDiagLen + ((tp0 ? (uint32_t)kDiagLenBounces : 0u) + b0) * (uint32_t)kDiagLenBins +
+                                  min(segs, (uint32_t)kDiagLenBins - 1u)], 1u);
         }
         mode = kIdle;
         max_segs = max(max_segs, segs);
@@ -1082,6 +736,77 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
                                 false, zero2, r);
         write_pixel_outputs(P, meta.x, r, h, FULL);
         next = r.next;
+    };
+    // a lane's shadow ray in LDS: six registers fewer across the shading code
+    auto sray_store = [&](f3 o, f3 d) {
+        lds_sray[0][threadIdx.x] = o.x;
+        lds_sray[1][threadIdx.x] = o.y;
+        lds_sray[2][threadIdx.x] = o.z;
+        lds_sray[3][threadIdx.x] = d.x;
+        lds_sray[4][threadIdx.x] = d.y;
+        lds_sray[5][threadIdx.x] = d.z;
+    };
+    auto sray_load = [&](uint32_t slot, f3& o, f3& d) {
+        o = mk3(lds_sray[0][slot], lds_sray[1][slot], lds_sray[2][slot]);
+        d = mk3(lds_sray[3][slot], lds_sray[4][slot], lds_sray[5][slot]);
+    };
+
+    // How a path advances is written once, for the three places it happens: the main loop, the lanes
+    // still waiting when the team drain begins, and the drain's leaders.  They differ in:
+    struct StepAt {
+        bool start_next;   // the lane starts its next closest-hit query itself (trav_start); before and in
+                           // the drain the team's start does it for every member, from the leader's ray
+        bool in_regs;      // a shadow ray's contribution waits in `contrib` and its tmax in T.best (set by
+                           // trav_start, which the loop needs anyway and the hand-over to the leaders
+                           // reads); in the drain both wait in the leader's lds_tx slot
+        bool fresh;        // a new query sets `fresh`: the leader's team starts it in its next iteration
+    };
+    constexpr StepAt kInLoop = {true, true, false}, kBeforeDrain = {false, true, false}, kInDrain = {false, false, true};
+    bool fresh = false;
+    auto next_query = [&](const StepAt at) {   // the path's next ray (rayO, rayD)
+        if (at.start_next) trav_start(T, rayO, rayD, INFINITY);
+        mode = kClosest;
+        n_closest++;
+        segs++;
+        if (at.fresh) fresh = true;
+    };
+    // this lane's query ended (any: the shadow ray's, occluded or not; else the closest-hit one's)
+    auto query_ended = [&](const StepAt at, bool any, bool occluded) {
+        if (any) {   // unoccluded -> add its contribution (:741-743)
+            if (!occluded)
+                p.accum = p.accum + (at.in_regs ? contrib
+                                                : mk3(lds_tx[1][threadIdx.x], lds_tx[2][threadIdx.x], lds_tx[3][threadIdx.x]));
+            if (next) next_query(at);
+            else end_path();
+        } else if (T.best_id == 0xffffffffu) {   // miss -> path ends (:321-322)
+            end_path();
+        } else {
+            mode = kReady;
+        }
+    };
+    // this lane's hit is shaded: its path goes on with the shadow ray, with the next ray, or ends
+    auto path_step = [&](const StepAt at) {
+        StepResult r;
+        shade_hit(r);
+        if (r.shadow) {
+            if (at.in_regs) {
+                contrib = r.contrib;
+                trav_start(T, r.so, r.sd, r.stmax);
+            } else {
+                lds_tx[0][threadIdx.x] = r.stmax;
+                lds_tx[1][threadIdx.x] = r.contrib.x;
+                lds_tx[2][threadIdx.x] = r.contrib.y;
+                lds_tx[3][threadIdx.x] = r.contrib.z;
+            }
+            sray_store(r.so, r.sd);
+            mode = kShadow;
+            n_shadow++;
+            if (at.fresh) fresh = true;
+        } else if (r.next) {
+            next_query(at);
+        } else {
+            end_path();
+        }
     };
 
     while (true) {
@@ -1113,22 +838,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
                     const float4* src = qin + 2 * (size_t)e;
                     const float4 o = ld_stream(&src[0]);
                     const float4 d = ld_stream(&src[1]);
-                    pid = __float_as_uint(o.w);
-                    const uint32_t state = __float_as_uint(d.w);
-                    const float4 c = state == 0u ? make_float4(1.0f, 1.0f, 1.0f, 0.0f)
-                                     : ld_stream(&Q.W.qc[cur][e]);
-                    if ((state & 0xffu) != 0u) {   // past bounce 0: the Halton index from qc.w (wf_shade)
-                        meta = make_uint4(0u, 1u, state, __float_as_uint(c.w));
-                    } else {
-                        const uint3 pm = path_meta(P, Q, pid);
-                        meta = make_uint4(pm.x, pm.y, state, pm.z);
-                    }
-                    const float4 a = Q.W.p_accum[pid];
-                    p.color = mk3(c.x, c.y, c.z);
-                    p.accum = mk3(a.x, a.y, a.z);
-                    p.bounce = (int)(meta.z & 0xffu);
-                    p.tpass = (int)((meta.z >> 8) & 0xffu);
-                    p.step = (int)(meta.z >> 16);
+                    load_path(P, Q, o, d, [&]() { return ld_stream(&Q.W.qc[cur][e]); }, true, pid, meta, p);
                     rayO = ld3(o);
                     rayD = ld3(d);
                     trav_start(T, rayO, rayD, INFINITY);
@@ -1149,21 +859,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
         if (mode == kClosest || mode == kShadow) {
             const bool any = mode == kShadow;
             if (trav_step<COUNT>(S, T, any, stack, tc, overflow, T.best)) {
-                if (any) {   // shadow ray done: unoccluded -> add its contribution (:741-743)
-                    if (!T.hit_any) p.accum = p.accum + contrib;
-                    if (next) {
-                        trav_start(T, rayO, rayD, INFINITY);
-                        mode = kClosest;
-                        n_closest++;
-                        segs++;
-                    } else {
-                        end_path();
-                    }
-                } else if (T.best_id == 0xffffffffu) {   // miss -> path ends (:321-322)
-                    end_path();
-                } else {
-                    mode = kReady;
-                }
+                query_ended(kInLoop, any, T.hit_any);
             }
         }
 
@@ -1177,35 +873,14 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
                 ++n_pass;
                 n_shaded += (uint32_t)__popcll(ready);
             }
-            if (mode == kReady) {
-                StepResult r;
-                shade_hit(r);
-                if (r.shadow) {
-                    contrib = r.contrib;
-                    trav_start(T, r.so, r.sd, r.stmax);
-                    lds_sray[0][threadIdx.x] = r.so.x;
-                    lds_sray[1][threadIdx.x] = r.so.y;
-                    lds_sray[2][threadIdx.x] = r.so.z;
-                    lds_sray[3][threadIdx.x] = r.sd.x;
-                    lds_sray[4][threadIdx.x] = r.sd.y;
-                    lds_sray[5][threadIdx.x] = r.sd.z;
-                    mode = kShadow;
-                    n_shadow++;
-                } else if (r.next) {
-                    trav_start(T, rayO, rayD, INFINITY);
-                    mode = kClosest;
-                    n_closest++;
-                    segs++;
-                } else {
-                    end_path();
-                }
-            }
+            if (mode == kReady) path_step(kInLoop);
             // Every lane's ray setup is rebuilt from its ray (a pure function of it, so bit for bit
             // the one trav_start made): the ~19 registers of the traversing lanes' setups are then
             // dead while the shading code runs, which sets the kernel's register peak.
             if (mode == kShadow) {
-                T.R = ray_setup(mk3(lds_sray[0][threadIdx.x], lds_sray[1][threadIdx.x], lds_sray[2][threadIdx.x]),
-                                mk3(lds_sray[3][threadIdx.x], lds_sray[4][threadIdx.x], lds_sray[5][threadIdx.x]));
+                f3 so, sd;
+                sray_load(threadIdx.x, so, sd);
+                T.R = ray_setup(so, sd);
             } else {
                 T.R = ray_setup(rayO, rayD);
             }
@@ -1223,28 +898,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
     // leader shades, then the team starts the path's next query.
     if (TEAM && __ballot(mode != kIdle) != 0ull) {
         const int TM = Q.team;
-        if (mode == kReady) {   // waiting lanes first: every busy lane then holds a query
-            StepResult r;
-            shade_hit(r);
-            if (r.shadow) {
-                contrib = r.contrib;
-                trav_start(T, r.so, r.sd, r.stmax);
-                lds_sray[0][threadIdx.x] = r.so.x;
-                lds_sray[1][threadIdx.x] = r.so.y;
-                lds_sray[2][threadIdx.x] = r.so.z;
-                lds_sray[3][threadIdx.x] = r.sd.x;
-                lds_sray[4][threadIdx.x] = r.sd.y;
-                lds_sray[5][threadIdx.x] = r.sd.z;
-                mode = kShadow;
-                n_shadow++;
-            } else if (r.next) {
-                mode = kClosest;
-                n_closest++;
-                segs++;
-            } else {
-                end_path();
-            }
-        }
+        if (mode == kReady) path_step(kBeforeDrain);   // waiting lanes first: every busy lane then holds a query
         const unsigned long long busy = __ballot(mode != kIdle);
         const int lane = (int)lane_id(), j = lane & (TM - 1), lead = lane - j, rk = lane / TM;
         const int nb = __popcll(busy);
@@ -1263,16 +917,13 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
         auto mv3 = [&](f3 v) { return mk3(mvf(v.x), mvf(v.y), mvf(v.z)); };
         const uint32_t sbase = threadIdx.x & ~63u;
         // the leaders' shadow rays stay in LDS (each leader's slot; the members read it when the
-        // team starts the query): six registers fewer across the shading code
+        // team starts the query)
         {
-            float sr[6];
-            #pragma unroll
-            for (int c = 0; c < 6; ++c) sr[c] = lds_sray[c][sbase + src];
-            #pragma unroll
-            for (int c = 0; c < 6; ++c) lds_sray[c][threadIdx.x] = sr[c];
+            f3 so, sd;
+            sray_load(sbase + (uint32_t)src, so, sd);
+            sray_store(so, sd);
         }
         // the leaders' shadow tmax and contribution stay in LDS as well (lds_tx)
-        __shared__ float lds_tx[4][kBlock];
         {
             const float t_src = mvf(T.best);
             const f3 c_src = mv3(contrib);
@@ -1296,7 +947,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
         // (inactive) non-leader source lanes as zero
         const int src_mode = (int)mvu((uint32_t)mode);
         mode = leader ? src_mode : kIdle;
-        bool fresh = leader;   // the team starts the leader's query
+        fresh = leader;   // the team starts the leader's query
         float cull = INFINITY;
         while (true) {
             const int lmode = __shfl(mode, lead);
@@ -1307,8 +958,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
                 float tmax;
                 if (any) {
                     const uint32_t ls = sbase + (uint32_t)lead;
-                    o = mk3(lds_sray[0][ls], lds_sray[1][ls], lds_sray[2][ls]);
-                    d = mk3(lds_sray[3][ls], lds_sray[4][ls], lds_sray[5][ls]);
+                    sray_load(ls, o, d);
                     tmax = lds_tx[0][ls];
                 } else {
                     o = mk3(__shfl(rayO.x, lead), __shfl(rayO.y, lead), __shfl(rayO.z, lead));
@@ -1360,9 +1010,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
                 }
                 const uint32_t got = (uint32_t)__shfl_xor((int)pay, k);
                 if (idle_m && p_give) {
-                    T.g_base = got >> 9;
-                    T.g_flip = (got >> 8) & 1u;
-                    T.g_hits = got & 0xffu;
+                    unpack_group(got, T.g_base, T.g_flip, T.g_hits);
                 }
             }
             // the team's query has ended once no member holds work
@@ -1390,51 +1038,9 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
                     T.bv = bv;
                     T.bdet = bd;
                 }
-                if (j == 0) {   // the leader: the path's next step (as in the loop above)
-                    if (any) {
-                        if (!hit)
-                            p.accum = p.accum + mk3(lds_tx[1][threadIdx.x], lds_tx[2][threadIdx.x], lds_tx[3][threadIdx.x]);
-                        if (next) {
-                            mode = kClosest;
-                            n_closest++;
-                            segs++;
-                            fresh = true;
-                        } else {
-                            end_path();
-                        }
-                    } else if (T.best_id == 0xffffffffu) {
-                        end_path();
-                    } else {
-                        mode = kReady;
-                    }
-                }
+                if (j == 0) query_ended(kInDrain, any, hit != 0);   // the leader: the path's next step
             }
-            if (mode == kReady) {   // leaders: shade at once (the drain is latency-bound)
-                StepResult r;
-                shade_hit(r);
-                if (r.shadow) {
-                    lds_tx[1][threadIdx.x] = r.contrib.x;
-                    lds_tx[2][threadIdx.x] = r.contrib.y;
-                    lds_tx[3][threadIdx.x] = r.contrib.z;
-                    lds_sray[0][threadIdx.x] = r.so.x;
-                    lds_sray[1][threadIdx.x] = r.so.y;
-                    lds_sray[2][threadIdx.x] = r.so.z;
-                    lds_sray[3][threadIdx.x] = r.sd.x;
-                    lds_sray[4][threadIdx.x] = r.sd.y;
-                    lds_sray[5][threadIdx.x] = r.sd.z;
-                    lds_tx[0][threadIdx.x] = r.stmax;
-                    mode = kShadow;
-                    n_shadow++;
-                    fresh = true;
-                } else if (r.next) {
-                    mode = kClosest;
-                    n_closest++;
-                    segs++;
-                    fresh = true;
-                } else {
-                    end_path();
-                }
-            }
+            if (mode == kReady) path_step(kInDrain);   // leaders: shade at once (the drain is latency-bound)
         }
     }
 
@@ -1449,7 +1055,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
             atomicAdd(&Q.W.counts[kWfStat + kStatDiagTPre], t_x);
             atomicAdd(&Q.W.counts[kWfStat + kStatDiagTPost], dt - t_x);
             atomicAdd(&Q.W.counts[kWfStat + kStatDiagLanesPost], x ? dx[2] : 0u);
-            atomicAdd(&Q.W.counts[kWfDiagExh + min(t_x / 5000u, 63u)], 1u);
+            atomicAdd(&Q.W.counts[kWfDiagExh + min(t_x / kDiagTimeBinTicks, (uint32_t)kDiagTimeBins - 1u)], 1u);
             atomicAdd(&Q.W.counts[kWfStat + kStatDiagShadeT], (uint32_t)t_shade);
             atomicAdd(&Q.W.counts[kWfStat + kStatDiagTotalT], dt);
             atomicAdd(&Q.W.counts[kWfStat + kStatDiagPasses], n_pass);
@@ -1460,7 +1066,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
             atomicMax(&Q.W.counts[cslot(kCntDiagSegs)], max_segs);
             atomicMax(&Q.W.counts[cslot(kCntDiagIters)], iters);
             atomicMax(&Q.W.counts[cslot(kCntDiagTime)], dt);
-            atomicAdd(&Q.W.counts[kWfDiagHist + min(dt / 5000u, 63u)], 1u);
+            atomicAdd(&Q.W.counts[kWfDiagHist + min(dt / kDiagTimeBinTicks, (uint32_t)kDiagTimeBins - 1u)], 1u);
         }
     }
 #undef RT_DX
@@ -1483,7 +1089,7 @@ __global__ void __launch_bounds__(kBlock) wf_extra(DevScene S, const FrameParams
     int px = 0, py = 0, e = 0;
     uint32_t pix = 0;
     if (i < Q.own_pixels) {
-        own_pixel(Q, i, px, py);
+        own_pixel(Q.px, i, px, py);
         if (px < U.width && py < U.height) {
             pix = (uint32_t)py * (uint32_t)U.width + (uint32_t)px;
             float2 mv2 = P.motion[pix], pm2 = P.motion_prev[pix];
@@ -1530,7 +1136,7 @@ __global__ void __launch_bounds__(kBlock) wf_motion(DevScene S, const FrameParam
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= Q.own_pixels) return;
     int px, py;
-    own_pixel(Q, i, px, py);
+    own_pixel(Q.px, i, px, py);
     if (px >= U.width || py >= U.height) return;
     const size_t pix = (size_t)py * U.width + px;
     const uint4 ph = P.prim_hit[pix];
@@ -1549,7 +1155,7 @@ __global__ void __launch_bounds__(kBlock) wf_resolve(DevScene S, const FramePara
     uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= Q.own_pixels) return;
     int px, py;
-    own_pixel(Q, i, px, py);
+    own_pixel(Q.px, i, px, py);
     if (px >= U.width || py >= U.height) return;
     size_t pix = (size_t)py * U.width + px;
     f3 total = mk3(0.0f, 0.0f, 0.0f);

@@ -15,7 +15,7 @@
 namespace rt {
 
 // Segment k only receives entries from blocks b == k (mod 8): at most n/8 + 256 per pass over n
-// inputs, and (own pixels/8 + 256) * maxExtra from the extra-sample pass.
+// inputs, and (own pixels/8 + 256) * maxExtra from the extra-sample pass (the bound: rt_wf_queue.h).
 size_t wavefront_queue_entries(size_t paths, int max_extra) {
     return (size_t)kShards * (paths / kShards + 4096 + 256 * (size_t)max_extra);
 }
@@ -35,7 +35,7 @@ namespace {
 unsigned grid_for(uint32_t n, unsigned cap) {
     unsigned g = (unsigned)(((uint64_t)n + kBlock - 1) / kBlock);
     if (g > cap) g = cap;
-    g = (g + kShards - 1) / kShards * kShards;  // multiple of 8: segment bound (see rt_wavefront.hip)
+    g = (g + kShards - 1) / kShards * kShards;  // multiple of 8: segment bound (see rt_wf_queue.h)
     return g == 0 ? kShards : g;
 }
 
@@ -48,7 +48,7 @@ uint32_t queue_total(const uint32_t* h, int q) {   // q = 0, 1: a ray queue (bot
 int rounds_for(uint64_t paths, uint32_t tail) {
     if (paths < tail) return 0;
     int k = 2;
-    while (k < 16 && (paths >> (k - 1)) >= tail) ++k;
+    while (k < kTsRounds && (paths >> (k - 1)) >= tail) ++k;
     return k;
 }
 
@@ -61,31 +61,31 @@ void print_finish_diag(const uint32_t* h, int it, uint32_t n, float ms) {
     const double np = h[kWfStat + kStatDiagPasses], ns = h[kWfStat + kStatDiagShaded];
     fprintf(stderr, "[wf] finish: %.1f %% of wave time in shading passes, %.0f passes, %.1f lanes per pass\n",
             tt > 0 ? 100.0 * st / tt : 0.0, np, np > 0 ? ns / np : 0.0);
-    for (int cl = 0; cl < 18; ++cl) {
+    for (int cl = 0; cl < kDiagLenClasses; ++cl) {
         uint32_t tot = 0;
         double sum = 0;
-        for (int b = 0; b < 32; ++b) {
-            tot += h[kWfDiagLen + cl * 32 + b];
-            sum += (double)b * h[kWfDiagLen + cl * 32 + b];
+        for (int b = 0; b < kDiagLenBins; ++b) {
+            tot += h[kWfDiagLen + cl * kDiagLenBins + b];
+            sum += (double)b * h[kWfDiagLen + cl * kDiagLenBins + b];
         }
         if (!tot) continue;
-        fprintf(stderr, "[wf] finish paths entering at bounce %d%s: %u, segments mean %.2f:", cl % 9,
-                cl >= 9 ? " refracting" : "", tot, sum / tot);
-        for (int b = 0; b < 32; ++b)
-            if (h[kWfDiagLen + cl * 32 + b]) fprintf(stderr, " %d:%u", b, h[kWfDiagLen + cl * 32 + b]);
+        fprintf(stderr, "[wf] finish paths entering at bounce %d%s: %u, segments mean %.2f:", cl % kDiagLenBounces,
+                cl >= kDiagLenBounces ? " refracting" : "", tot, sum / tot);
+        for (int b = 0; b < kDiagLenBins; ++b)
+            if (h[kWfDiagLen + cl * kDiagLenBins + b]) fprintf(stderr, " %d:%u", b, h[kWfDiagLen + cl * kDiagLenBins + b]);
         fprintf(stderr, "\n");
     }
     fprintf(stderr, "[wf] finish wave end times (50 us bins):");
-    for (int b = 0; b < 64; ++b)
+    for (int b = 0; b < kDiagTimeBins; ++b)
         if (h[kWfDiagHist + b]) fprintf(stderr, " %d:%u", b, h[kWfDiagHist + b]);
     fprintf(stderr, "\n[wf] finish queue exhausted at (50 us bins):");
-    for (int b = 0; b < 64; ++b)
+    for (int b = 0; b < kDiagTimeBins; ++b)
         if (h[kWfDiagExh + b]) fprintf(stderr, " %d:%u", b, h[kWfDiagExh + b]);
     const double ip = h[kWfStat + kStatDiagItPre], ix = h[kWfStat + kStatDiagItPost];
     const double tp = h[kWfStat + kStatDiagTPre], tx = h[kWfStat + kStatDiagTPost];
     const double lx = h[kWfStat + kStatDiagLanesPost];
     double waves = 0;
-    for (int b = 0; b < 64; ++b) waves += h[kWfDiagHist + b];
+    for (int b = 0; b < kDiagTimeBins; ++b) waves += h[kWfDiagHist + b];
     waves = waves > 0 ? waves : 1;
     fprintf(stderr, "\n[wf] finish per wave: %.0f iterations at %.2f us before its queue ran out, %.0f at %.2f us "
             "after (%.1f active lanes)\n", ip / waves, ip > 0 ? tp * 0.01 / ip : 0.0, ix / waves,
@@ -98,9 +98,9 @@ void print_round_diag(const uint32_t* h, int it, uint32_t n, const float (&ms)[4
             queue_total(h, 2), ms[0], ms[1], ms[2], ms[3]);
     if (!count) return;
     for (int any = 0; any < 2; ++any) {
-        fprintf(stderr, "[wf]   %s steps/ray log2 bins (max %u):", any ? "connect" : "extend", h[kWfDiagSteps + 64 + any]);
-        for (int b = 0; b < 32; ++b)
-            if (h[kWfDiagSteps + 32 * any + b]) fprintf(stderr, " %d:%u", b, h[kWfDiagSteps + 32 * any + b]);
+        fprintf(stderr, "[wf]   %s steps/ray log2 bins (max %u):", any ? "connect" : "extend", h[kWfDiagSteps + 2 * kDiagStepBins + any]);
+        for (int b = 0; b < kDiagStepBins; ++b)
+            if (h[kWfDiagSteps + kDiagStepBins * any + b]) fprintf(stderr, " %d:%u", b, h[kWfDiagSteps + kDiagStepBins * any + b]);
         fprintf(stderr, "\n");
     }
 }
@@ -219,9 +219,9 @@ struct Frame {
         WF_CHECK(hipEventRecord(W.ev[0], stream));
         WF_CHECK(hipMemsetAsync(W.counts + cslot(kCntChunkFinish), 0, cslot(kShards) * sizeof(uint32_t), stream));
         if (Q.diag) {
-            WF_CHECK(hipMemsetAsync(W.counts + kWfDiagHist, 0, 64 * sizeof(uint32_t), stream));
-            WF_CHECK(hipMemsetAsync(W.counts + kWfDiagExh, 0, 64 * sizeof(uint32_t), stream));
-            WF_CHECK(hipMemsetAsync(W.counts + kWfStat + kStatDiagShadeT, 0, (kWfStatWords - kStatDiagShadeT) * sizeof(uint32_t),
+            WF_CHECK(hipMemsetAsync(W.counts + kWfDiagHist, 0, kDiagTimeBins * sizeof(uint32_t), stream));
+            WF_CHECK(hipMemsetAsync(W.counts + kWfDiagExh, 0, kDiagTimeBins * sizeof(uint32_t), stream));
+            WF_CHECK(hipMemsetAsync(W.counts + kWfStat + kStatDiagShadeT, 0, kStatDiagWords * sizeof(uint32_t),
                                     stream));
         }
         if (!launch_finish(cur, n, -1)) return false;
@@ -258,7 +258,7 @@ struct Frame {
             fs->trace_ms += ms[0] + ms[3];
             if (Q.diag) {
                 print_round_diag(W.h_counts, it, n, ms, count);
-                if (count) WF_CHECK(hipMemsetAsync(W.counts + kWfDiagSteps, 0, 66 * sizeof(uint32_t), stream));
+                if (count) WF_CHECK(hipMemsetAsync(W.counts + kWfDiagSteps, 0, kDiagStepsWords * sizeof(uint32_t), stream));
             }
             n = queue_total(W.h_counts, 1 - cur);
             cur = 1 - cur;
@@ -477,13 +477,13 @@ bool wavefront_collect(const WavefrontBuffers& W, WfTimeline& T, WfFrameStats* f
             const int slot = pass * kTsPass + k;
             const unsigned long long a = W.h_tstamp[slot * kTsStride];
             unsigned long long b = 0;
-            for (int x = 1; x <= 8; ++x) b = std::max(b, W.h_tstamp[slot * kTsStride + kTsLine * x]);
+            for (int x = 1; x <= kTsXcds; ++x) b = std::max(b, W.h_tstamp[slot * kTsStride + kTsLine * x]);
             if (a == 0 || b <= a) continue;
             const float ms = (float)((double)(b - a) * 1e-5);
             if (k == kTsFinish) {
                 fs->finish_dev_ms += ms;
                 fs->finish_dev_launches++;
-            } else if (k < 2 * 16) {
+            } else if (k < 2 * kTsRounds) {
                 fs->trace_dev_ms += ms;
                 fs->trace_dev_launches++;
             }
@@ -513,12 +513,12 @@ bool run_wavefront(const DevScene& S, const FrameParams& P, WavefrontBuffers& W,
     Q.fchunk = tu.fchunk;
     Q.shade_blocks = tu.shade_blocks;
     Q.spans = spans ? 1 : 0;
-    Q.spp_div = make_fastdiv((uint32_t)Q.spp);
-    Q.tile = P.tile_size;
-    Q.rank = P.rank;
-    Q.nranks = P.nranks;
-    Q.tile_px_div = make_fastdiv((uint32_t)P.tile_size * (uint32_t)P.tile_size);
-    Q.tiles_x_div = make_fastdiv((uint32_t)max(P.tiles_x, 1));
+    Q.px.spp_div = make_fastdiv((uint32_t)Q.spp);
+    Q.px.tile = P.tile_size;
+    Q.px.rank = P.rank;
+    Q.px.nranks = P.nranks;
+    Q.px.tile_px_div = make_fastdiv((uint32_t)P.tile_size * (uint32_t)P.tile_size);
+    Q.px.tiles_x_div = make_fastdiv((uint32_t)max(P.tiles_x, 1));
     Q.trace_frac = sched.trace_frac;
     Q.finish_frac = sched.finish_frac;
     if (sort_bins && (sort_bins < kSortMinBins || sort_bins > kSortMaxBins || (sort_bins & (sort_bins - 1)) ||

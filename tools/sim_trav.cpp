@@ -2,7 +2,7 @@
 //
 // Builds the C3g scene's 8-wide BVH with the product's host builder, makes extend rays (primary
 // rays of a pixel grid, then one diffuse bounce from their hits), and replays the per-lane
-// traversal of trav_step (rt_wavefront.hip) wave by wave (64 lanes, per-lane refill from a ray
+// traversal of trav_step (rt_trav.h) wave by wave (64 lanes, per-lane refill from a ray
 // stream).  A wave iteration costs the VALU issues of every code block that at least one lane
 // executes (block costs from the gfx950 ISA of wf_trace<false,false>); the model reports
 // issues per ray and iterations per ray for several schedules, to rank them before a GPU A/B.
