@@ -23,6 +23,8 @@
  *                              depth/motion/G-buffer targets (Renderer.swift:676-804)
  *   rt_render_frame            Renderer.draw: argument-table binding + 16x16 dispatch of
  *                              raytracingKernel + ping-pong swap (Renderer.swift:1405-1503)
+ *   rt_trace_closest/rt_trace_any  `intersector.intersect` called from any other kernel: batches
+ *                              of the caller's rays against the built scene
  *   rt_read_radiance/rt_read_aux  (no reference equivalent: the reference never reads back;
  *                              replaces presenting dstTex/depthTex/motionTex to MetalFX)
  *
@@ -361,6 +363,81 @@ typedef struct rt_tuning {
 } rt_tuning;
 rt_status rt_set_tuning(rt_ctx* ctx, const rt_tuning* tuning);
 rt_status rt_get_tuning(const rt_ctx* ctx, rt_tuning* out);
+
+/* ---- device ray queries ---------------------------------------------------------------------
+ * The reference's `intersector.intersect` outside raytracingKernel (any Metal kernel may call
+ * it): trace a batch of the caller's rays against the built scene on the GPU.  `rays`, `hits`
+ * and `occluded` are DEVICE pointers; the calls enqueue one kernel launch and return without a
+ * host wait (results are ordered on the stream the query ran on; rt_wait waits for them too).
+ *
+ * Both records are 32 B, 16-byte aligned, and read / written as two 16-B words. */
+typedef struct rt_ray {      /* 32 B */
+    float origin[3];
+    float reserved;          /* ignored */
+    float direction[3];      /* need not be unit length; t is in units of it */
+    float tmax;              /* hits with t in [0, tmax]; INFINITY = unbounded */
+} rt_ray;
+
+#define RT_MISS 0xffffffffu
+typedef struct rt_ray_hit {  /* 32 B */
+    float t;                 /* INFINITY on a miss */
+    float u, v;              /* barycentrics in the library's convention (u -> v1, v -> v2); 0 on a miss */
+    uint32_t triangle;       /* scene-wide triangle id (meshes, then submeshes, in upload order); RT_MISS */
+    uint32_t mesh;           /* instance_id of Metal's intersection result; RT_MISS */
+    uint32_t submesh;        /* geometry_id; RT_MISS */
+    uint32_t primitive;      /* primitive_id: triangle index within the submesh; RT_MISS */
+    uint32_t reserved;       /* 0 */
+} rt_ray_hit;
+
+/* The last query's figures and the running totals since rt_create (a separate struct: rt_stats
+ * keeps its layout).  Node visits and triangle tests are counted only by queries enqueued while
+ * rt_set_counting is on. */
+typedef struct rt_query_stats {
+    uint64_t rays;           /* rays of the last query */
+    uint64_t hits;           /* closest-hit: rays that hit; any-hit: occluded rays */
+    uint64_t node_visits;
+    uint64_t tri_tests;
+    uint32_t grid_blocks;    /* blocks of 256 threads the launch took */
+    int32_t any_hit;         /* the last query was rt_trace_any */
+    float device_ms;         /* device time of the launch (HIP events around it) */
+    uint32_t reserved;
+    uint64_t queries_total;  /* queries launched (n > 0) */
+    uint64_t total_rays;
+    uint64_t total_hits;
+    uint64_t total_node_visits;
+    uint64_t total_tri_tests;
+    uint64_t total_grid_blocks;
+    double total_device_ms;
+} rt_query_stats;
+
+/* Semantics:
+ *  - Closest hit follows the renderer's rule: nearest t, ties to the lower triangle id.  The result
+ *    is independent of which builder made the tree and bit-identical to rt_debug_trace_host on the
+ *    same geometry.  Any hit reports occlusion only (1 / 0 per ray): which occluder is found
+ *    depends on the tree, so none is returned.
+ *  - Geometry seen: exactly what the next rt_render_frame would see, i.e. the newest committed
+ *    geometry generation; the query's stream first waits for the update stream (skinning,
+ *    transforms, refit enqueued before the call).
+ *  - No race with updates: rt_skin, rt_set_instance_transforms, rt_bvh_refit, both builds, the
+ *    automatic rebuild and rt_scene_upload first wait, on the host, for every pending query.
+ *  - rt_wait and rt_destroy wait for queries too.  Frames share nothing writable with queries:
+ *    frames rendered with queries interleaved are bit-identical to frames rendered without.
+ *  - Back-to-back queries, also on different streams, need no host wait between them: each
+ *    launch owns one of a small ring of device states (chunk counters, statistics); a state is
+ *    reused only once its previous query has finished.
+ *  - Needs only the scene and a BVH (either pipeline; no rt_resize).
+ *  - The plain forms run on the context's stream, the _on forms on `hip_stream` exactly as
+ *    given (NULL is HIP's null stream), as rt_pack_tiles / rt_pack_tiles_on do.
+ *  - Errors: a NULL pointer with n > 0, or a pointer not 16-byte aligned (4-byte for
+ *    `occluded`): RT_ERR_INVALID_ARG.  Before a BVH build: RT_ERR_STATE.  n == 0: RT_OK, nothing
+ *    is launched.  A traversal-stack overflow is counted on the device and returned as
+ *    RT_ERR_STATE by the next rt_wait or rt_get_query_stats, as frames report theirs.
+ *  - rt_get_query_stats waits for pending queries before it reads. */
+rt_status rt_trace_closest(rt_ctx* ctx, const rt_ray* rays, uint32_t n, rt_ray_hit* hits);
+rt_status rt_trace_any(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t* occluded);
+rt_status rt_trace_closest_on(rt_ctx* ctx, const rt_ray* rays, uint32_t n, rt_ray_hit* hits, void* hip_stream);
+rt_status rt_trace_any_on(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t* occluded, void* hip_stream);
+rt_status rt_get_query_stats(rt_ctx* ctx, rt_query_stats* out);
 
 /* Library build identification (kernel code object arch etc). */
 const char* rt_version(void);

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (TEXTURE_SLOTS, Tuning, Camera, Float3, Light, MaterialOverride, PackedFloat4x3, SceneDesc, Stats, TextureDesc,
-                   TileSet, Uniforms,
+                   TileSet, Uniforms, Ray, RayHit, QueryStats,
                    f3)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -296,6 +296,20 @@ def _tuning_struct(fields):
     return t
 
 
+class Hits:
+    """Closest-hit results of Renderer.trace: `buffer` holds the (n, 8) rt_ray_hit records and the
+    fields are views of it: float32 t (inf on a miss), u, v; int32 triangle, mesh, submesh,
+    primitive (-1 on a miss).  Torch tensors on the device path, numpy arrays on the host path."""
+
+    def __init__(self, buffer, as_int):
+        self.buffer = buffer
+        self.t, self.u, self.v = buffer[:, 0], buffer[:, 1], buffer[:, 2]
+        self.triangle, self.mesh, self.submesh, self.primitive = (as_int[:, k] for k in (3, 4, 5, 6))
+
+    def __len__(self):
+        return self.buffer.shape[0]
+
+
 class Renderer:
     """Renderer.swift for the hot path: owns a device context, the uniforms and the frame index.
 
@@ -317,6 +331,7 @@ class Renderer:
         ctx = C.c_void_p()
         _check(lib().rt_create(C.byref(opts), C.byref(ctx)))
         object.__setattr__(self, "_ctx", ctx)
+        self.device = int(device)
         if stream is not None:
             _check(lib().rt_set_stream(ctx, C.c_void_p(stream)), ctx)
         if tuning:
@@ -395,6 +410,80 @@ class Renderer:
     def stats(self):
         s = Stats()
         _check(lib().rt_get_stats(self._ctx, C.byref(s)), self._ctx)
+        return s
+
+    # --- device ray queries (intersector.intersect outside raytracingKernel) ---
+    @staticmethod
+    def make_rays(origins, dirs, tmax=None):
+        """(n, 8) float32 rt_ray records (origin, 0, direction, tmax; tmax None = unbounded) from
+        (n, 3) origins and directions: a torch tensor on their device when they are tensors, a
+        numpy array otherwise."""
+        try:
+            import torch
+            on_torch = isinstance(origins, torch.Tensor)
+        except ImportError:
+            on_torch = False
+        if on_torch:
+            o = origins.reshape(-1, 3).to(torch.float32)
+            r = torch.zeros((o.shape[0], 8), dtype=torch.float32, device=o.device)
+            r[:, 0:3] = o
+            r[:, 4:7] = dirs.reshape(-1, 3).to(torch.float32)
+            r[:, 7] = float("inf") if tmax is None else torch.as_tensor(tmax, dtype=torch.float32, device=o.device)
+            return r
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        r = np.zeros((o.shape[0], 8), np.float32)
+        r[:, 0:3] = o
+        r[:, 4:7] = np.asarray(dirs, np.float32).reshape(-1, 3)
+        r[:, 7] = np.inf if tmax is None else np.asarray(tmax, np.float32)
+        return r
+
+    def trace(self, rays, any_hit=False, out=None, stream=None):
+        """rt_trace_closest / rt_trace_any: traces (n, 8) rays (make_rays) against the geometry the
+        next draw() would see.
+
+        Device path: `rays` is a contiguous float32 torch tensor on the renderer's device, read in
+        place; the query is enqueued on `stream` (a HIP stream handle as in pack_tiles: 0 = HIP's
+        null stream, torch's default; None = the renderer's stream) without a host wait, and the
+        caller orders `rays` (and `out`: (n, 8) float32, or (n,) int32 for any_hit) before that
+        stream.  Returns Hits (views of one (n, 8) tensor), or one int32 tensor of 1 / 0 for any_hit.
+
+        Host path: `rays` is a host array; it is staged through torch, the query is waited for and
+        the result comes back as numpy."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = not isinstance(rays, torch.Tensor)
+        if host:
+            r = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
+        else:
+            r = rays
+            if r.dtype != torch.float32 or r.dim() != 2 or r.shape[1] != 8 or not r.is_contiguous() or r.device != dev:
+                raise ValueError(f"rays must be a contiguous float32 (n, 8) tensor on {dev}")
+        n = r.shape[0]
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int32, device=dev) if any_hit else \
+                torch.empty((n, 8), dtype=torch.float32, device=dev)
+        else:
+            want = ((n,), torch.int32) if any_hit else ((n, 8), torch.float32)
+            if tuple(out.shape) != want[0] or out.dtype != want[1] or not out.is_contiguous() or out.device != dev:
+                raise ValueError(f"out must be a contiguous {want[1]} tensor of shape {want[0]} on {dev}")
+        if host:
+            torch.cuda.current_stream(dev).synchronize()   # the staging copy and the allocator's stream
+        L = lib()
+        args = (self._ctx, C.c_void_p(r.data_ptr()), n, C.c_void_p(out.data_ptr()))
+        if stream is None:
+            _check((L.rt_trace_any if any_hit else L.rt_trace_closest)(*args), self._ctx)
+        else:
+            _check((L.rt_trace_any_on if any_hit else L.rt_trace_closest_on)(*args, C.c_void_p(stream)), self._ctx)
+        if host:
+            self.wait()
+            res = out.cpu().numpy()
+            return res if any_hit else Hits(res, res.view(np.int32))
+        return out if any_hit else Hits(out, out.view(torch.int32))
+
+    def query_stats(self):
+        """rt_get_query_stats (waits for pending queries): the last query and the running totals."""
+        s = QueryStats()
+        _check(lib().rt_get_query_stats(self._ctx, C.byref(s)), self._ctx)
         return s
 
     def radiance(self):

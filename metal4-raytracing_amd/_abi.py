@@ -196,6 +196,38 @@ class Stats(C.Structure):
     ]
 
 
+class Ray(C.Structure):  # rt_ray: 32 B, two 16-B words
+    _fields_ = [("origin", C.c_float * 3), ("reserved", C.c_float), ("direction", C.c_float * 3), ("tmax", C.c_float)]
+
+
+RT_MISS = 0xFFFFFFFF
+
+
+class RayHit(C.Structure):  # rt_ray_hit: 32 B, two 16-B words
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_uint32), ("mesh", C.c_uint32),
+                ("submesh", C.c_uint32), ("primitive", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class QueryStats(C.Structure):  # rt_query_stats
+    _fields_ = [
+        ("rays", C.c_uint64),
+        ("hits", C.c_uint64),
+        ("node_visits", C.c_uint64),
+        ("tri_tests", C.c_uint64),
+        ("grid_blocks", C.c_uint32),
+        ("any_hit", C.c_int32),
+        ("device_ms", C.c_float),
+        ("reserved", C.c_uint32),
+        ("queries_total", C.c_uint64),
+        ("total_rays", C.c_uint64),
+        ("total_hits", C.c_uint64),
+        ("total_node_visits", C.c_uint64),
+        ("total_tri_tests", C.c_uint64),
+        ("total_grid_blocks", C.c_uint64),
+        ("total_device_ms", C.c_double),
+    ]
+
+
 class MaterialOverride(C.Structure):  # Model.swift:11-27
     _fields_ = [
         ("has_base_color", C.c_int32),
@@ -240,6 +272,7 @@ EXPORTED_SYMBOLS = [
     "rt_pack_tiles_on", "rt_unpack_tiles_on", "rt_present", "rt_write_png",
     "rt_pack_tiles_host", "rt_unpack_tiles_host",
     "rt_set_counting", "rt_set_device_spans", "rt_set_graphs", "rt_get_stats", "rt_set_tuning", "rt_get_tuning",
+    "rt_trace_closest", "rt_trace_any", "rt_trace_closest_on", "rt_trace_any_on", "rt_get_query_stats",
     "rt_version", "rt_debug_trace_host",
     # rt_scene.h
     "rt_material_override_glass", "rt_scene_new", "rt_scene_free", "rt_scene_last_error",
@@ -291,6 +324,11 @@ def declare(lib):
         "rt_get_stats": (st, [vp, P(Stats)]),
         "rt_set_tuning": (st, [vp, P(Tuning)]),
         "rt_get_tuning": (st, [vp, P(Tuning)]),
+        "rt_trace_closest": (st, [vp, vp, C.c_uint32, vp]),
+        "rt_trace_any": (st, [vp, vp, C.c_uint32, vp]),
+        "rt_trace_closest_on": (st, [vp, vp, C.c_uint32, vp, vp]),
+        "rt_trace_any_on": (st, [vp, vp, C.c_uint32, vp, vp]),
+        "rt_get_query_stats": (st, [vp, P(QueryStats)]),
         "rt_version": (C.c_char_p, []),
         "rt_debug_trace_host": (st, [P(SceneDesc), P(C.c_float), P(C.c_float), C.c_uint32, C.c_int32, P(C.c_float),
                                      P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32)]),

@@ -161,6 +161,8 @@ rt_status rt_destroy(rt_ctx* c) {
     if (c->ustream) (void)hipStreamSynchronize(c->ustream);
     for (FrameSlot& f : c->slot)
         if (f.own_stream) (void)hipStreamSynchronize(f.own_stream);
+    for (QuerySlot& q : c->qslot)   // ray queries, also those on a caller's stream
+        if (q.pending) (void)hipEventSynchronize(q.done);
     delete c;
     return RT_OK;
 }

@@ -258,9 +258,11 @@ rt_status issue_plan(rt_ctx* c, const FramePlan& pl, hipStream_t stream) {
     }
     if (pl.drain)
         if (rt_status st = drain_frames(c)) return st;
-    if (pl.regen)
+    if (pl.regen) {
+        if (rt_status st = drain_queries(c)) return st;   // a pending ray query may read a generation freed here
         for (int g = pl.ngens; g < kGens; ++g)
             for (DevBuf& b : c->geo[g].buf) dev_free(c, b);
+    }
     c->ring.begin_frame(pl);
     if (c->uev_valid) HIPC(c, hipStreamWaitEvent(stream, c->uev, 0));
     return RT_OK;
@@ -446,6 +448,11 @@ rt_status rt_wait(rt_ctx* c) {
     for (int k : order)
         if (rt_status st = harvest(c, k)) return st;
     if (c->ring.newest_used()) HIPC(c, hipEventSynchronize(c->slot[c->ring.last_slot].done));   // and a pack / unpack after it
+    if (rt_status st = drain_queries(c)) return st;   // ray queries, also those on a caller's stream
+    if (c->q_overflow) {
+        c->q_overflow = false;
+        FAIL(c, RT_ERR_STATE, "traversal stack overflow in a ray query");
+    }
     return RT_OK;
 }
 

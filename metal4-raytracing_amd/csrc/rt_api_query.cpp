@@ -1,0 +1,157 @@
+// rt_api_query.cpp — device ray queries: rt_trace_closest / rt_trace_any enqueue one rq_trace
+// launch (rt_query.hip) over the caller's device rays against the geometry generation the next
+// frame would read, and rt_get_query_stats reports them.  The replacement of Metal's
+// `intersector.intersect` called outside raytracingKernel.  Queries share nothing writable with
+// frames: their counters, events and statistics are their own (QuerySlot, rt_ctx.h).
+#include <algorithm>
+#include <cstring>
+
+#include "rt_ctx.h"
+
+using namespace rt;
+
+namespace {
+// Folds the finished query of slot k into rt_query_stats.  Waits for it: called before the slot
+// is reused and from drain_queries, oldest query first.
+rt_status harvest_query(rt_ctx* c, int k) {
+    QuerySlot& q = c->qslot[k];
+    if (!q.pending) return RT_OK;
+    q.pending = false;
+    HIPC(c, hipEventSynchronize(q.done));
+    float ms = 0.0f;
+    HIPC(c, hipEventElapsedTime(&ms, q.ev0, q.ev1));
+    const unsigned long long* hc = q.h_counters.get();
+    auto total = [hc](int word) {
+        unsigned long long t = 0;
+        for (int r = 0; r < kCntReplicas; ++r) t += hc[cnt_word(word, r)];
+        return t;
+    };
+    rt_query_stats& S = c->qstats;
+    S.rays = total(q.any ? kCntShadow : kCntClosest);
+    S.hits = total(kCntPaths);
+    S.node_visits = total(kCntNodes);
+    S.tri_tests = total(kCntTris);
+    S.grid_blocks = q.blocks;
+    S.any_hit = q.any ? 1 : 0;
+    S.device_ms = ms;
+    S.queries_total += 1;
+    S.total_rays += S.rays;
+    S.total_hits += S.hits;
+    S.total_node_visits += S.node_visits;
+    S.total_tri_tests += S.tri_tests;
+    S.total_grid_blocks += S.grid_blocks;
+    S.total_device_ms += ms;
+    if (total(kCntOverflow)) c->q_overflow = true;
+    return RT_OK;
+}
+
+// The slot's device state, pinned copy and events, made once.
+rt_status ensure_query_slot(rt_ctx* c, QuerySlot& q) {
+    if (q.done) return RT_OK;   // the last one made below: a call that failed half way starts over
+    if (rt_status st = dev_alloc(c, q.state, kRqStateBytes)) return st;
+    HIPC(c, q.h_counters.alloc(sizeof(unsigned long long) * kCounterWords));
+    HIPC(c, q.ev0.create());
+    HIPC(c, q.ev1.create());
+    HIPC(c, q.done.create(hipEventDisableTiming));
+    return RT_OK;
+}
+
+// own_stream: the ctx stream (rt_trace_closest / rt_trace_any); otherwise `stream` as the caller
+// gave it, the null stream included
+rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, hipStream_t stream, bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (n > 0) {
+        if (!rays || !out) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+        if (((uintptr_t)rays & 15u) || ((uintptr_t)out & (any ? 3u : 15u)))
+            FAIL(c, RT_ERR_INVALID_ARG, "rays / hits must be 16-byte aligned, occluded 4-byte aligned");
+    }
+    if (!c->bvh_ready) FAIL(c, RT_ERR_STATE, "ray query before rt_bvh_build");
+    if (n == 0) return RT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    if (own_stream) stream = c->stream;
+    QuerySlot& q = c->qslot[c->qnext];
+    rt_status st = harvest_query(c, c->qnext);   // the slot's previous query (kQuerySlots back) has finished
+    if (!st) st = ensure_query_slot(c, q);
+    if (st) return st;
+    // the geometry the next frame would read: the generation updates since the newest frame went
+    // into (after the update stream's work so far), else the one frames read (after the event of
+    // the flip that made it current)
+    if (c->ring.gdirty) {
+        if (!c->q_uev) HIPC(c, c->q_uev.create(hipEventDisableTiming));
+        HIPC(c, hipEventRecord(c->q_uev, c->ustream));
+        HIPC(c, hipStreamWaitEvent(stream, c->q_uev, 0));
+    } else if (c->uev_valid) {
+        HIPC(c, hipStreamWaitEvent(stream, c->uev, 0));
+    }
+    const Geo& geo = c->geo[c->ring.write_gen()];
+    DevScene S;
+    std::memset(&S, 0, sizeof S);   // the traversal reads the tree, the triangles and tri_info only
+    S.tris = (const float*)geo[Geo::tris].p;
+    S.nodes8 = (const Bvh8Node*)geo[Geo::nodes].p;
+    S.tri_info = (const uint4*)c->d_tri_info.p;
+    S.max_submeshes = c->max_sub;
+    S.num_tris = (int)c->num_tris;
+    S.num_nodes8 = (int)geo.num_nodes8;
+    RqParams Q;
+    Q.rays = (const float4*)rays;
+    Q.hits = any ? nullptr : (float4*)out;
+    Q.occluded = any ? (uint32_t*)out : nullptr;
+    Q.sub_first = (const uint32_t*)c->d_sub_first.p;
+    Q.state = (unsigned long long*)q.state.p;
+    Q.n = n;
+    Q.refill_min = c->tuning.refill_min;
+    // a small batch does not launch the whole chip
+    const unsigned blocks = std::min(query_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u);
+    HIPC(c, hipMemsetAsync(q.state.p, 0, kRqStateBytes, stream));
+    HIPC(c, hipEventRecord(q.ev0, stream));
+    launch_query(S, Q, any, c->counting, blocks, stream);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(q.ev1, stream));
+    HIPC(c, hipMemcpyAsync(q.h_counters, q.state.p, sizeof(unsigned long long) * kCounterWords, hipMemcpyDeviceToHost,
+                           stream));
+    HIPC(c, hipEventRecord(q.done, stream));
+    q.pending = true;
+    q.any = any;
+    q.blocks = blocks;
+    c->qnext = (c->qnext + 1) % kQuerySlots;
+    return RT_OK;
+}
+}  // namespace
+
+rt_status drain_queries(rt_ctx* c) {
+    for (int i = 0; i < kQuerySlots; ++i)   // qnext is the oldest slot
+        if (rt_status st = harvest_query(c, (c->qnext + i) % kQuerySlots)) return st;
+    return RT_OK;
+}
+
+extern "C" {
+
+rt_status rt_trace_closest(rt_ctx* c, const rt_ray* rays, uint32_t n, rt_ray_hit* hits) {
+    return trace(c, rays, n, hits, false, nullptr, true);
+}
+
+rt_status rt_trace_any(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t* occluded) {
+    return trace(c, rays, n, occluded, true, nullptr, true);
+}
+
+rt_status rt_trace_closest_on(rt_ctx* c, const rt_ray* rays, uint32_t n, rt_ray_hit* hits, void* stream) {
+    return trace(c, rays, n, hits, false, (hipStream_t)stream, false);
+}
+
+rt_status rt_trace_any_on(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t* occluded, void* stream) {
+    return trace(c, rays, n, occluded, true, (hipStream_t)stream, false);
+}
+
+rt_status rt_get_query_stats(rt_ctx* c, rt_query_stats* out) {
+    if (!c || !out) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+    HIPC(c, hipSetDevice(c->device));
+    if (rt_status st = drain_queries(c)) return st;
+    *out = c->qstats;
+    if (c->q_overflow) {
+        c->q_overflow = false;
+        FAIL(c, RT_ERR_STATE, "traversal stack overflow in a ray query");
+    }
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -87,8 +87,12 @@ void flatten_scene(const rt_scene_desc* sd, std::vector<float4>& pos, std::vecto
 
 // Before a geometry update: the first one after a frame switches to the next generation, once the
 // frames still reading it have finished, seeded with a copy of the current one (on the update
-// stream; frames keep reading the current generation meanwhile).
+// stream; frames keep reading the current generation meanwhile).  Every entry point that writes
+// geometry or the tree (skinning, transforms, refit, both builds and with them the automatic
+// rebuild) comes through here first, so this is also where they wait for pending ray queries: a
+// query reads the newest generation, which an update without a frame in between rewrites in place.
 rt_status begin_update(rt_ctx* c) {
+    if (rt_status st = drain_queries(c)) return st;
     const UpdatePlan u = c->ring.plan_update();
     if (!u.seed) return RT_OK;
     for (int k = 0; k < kMaxSlots; ++k)
@@ -264,6 +268,7 @@ extern "C" {
 rt_status rt_scene_upload(rt_ctx* c, const rt_scene_desc* sd) {
     if (!c || !sd) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
     if (rt_status dst = drain_frames(c)) return dst;
+    if (rt_status qst = drain_queries(c)) return qst;
     HIPC(c, hipSetDevice(c->device));
     int max_sub;
     uint64_t nv, nt;
@@ -281,6 +286,8 @@ rt_status rt_scene_upload(rt_ctx* c, const rt_scene_desc* sd) {
     c->meshes.assign(sd->mesh_count, MeshInfo());
     uint32_t vbase = 0, tri = 0;
     bool any_skin = false;
+    // ray queries' primitive ids: the first scene-wide triangle id of every submesh
+    std::vector<uint32_t> sub_first((size_t)max_sub * sd->mesh_count, 0u);
     for (uint32_t m = 0; m < sd->mesh_count; ++m) {
         const rt_mesh_desc& md = sd->meshes[m];
         MeshInfo& mi = c->meshes[m];
@@ -292,6 +299,7 @@ rt_status rt_scene_upload(rt_ctx* c, const rt_scene_desc* sd) {
         any_skin |= mi.skinned;
         for (uint32_t s = 0; s < md.submesh_count; ++s) {
             c->h_mat[(size_t)m * max_sub + s] = md.submeshes[s].material;
+            sub_first[(size_t)m * max_sub + s] = tri;
             tri += md.submeshes[s].index_count / 3;
         }
         vbase += md.vertex_count;
@@ -313,6 +321,7 @@ rt_status rt_scene_upload(rt_ctx* c, const rt_scene_desc* sd) {
     if ((st = dev_upload(c, g[Geo::prev_inst], c->h_inst.data(), c->h_inst.size() * 4))) return st;
     if ((st = dev_upload(c, c->d_mat, c->h_mat.data(), c->h_mat.size() * sizeof(Material)))) return st;
     if ((st = dev_upload(c, c->d_lights, c->h_lights.data(), c->h_lights.size() * sizeof(Light)))) return st;
+    if ((st = dev_upload(c, c->d_sub_first, sub_first.data(), sub_first.size() * 4))) return st;
     if (any_skin && (st = upload_skinning(c, sd))) return st;
     HIPC(c, hipStreamSynchronize(c->stream));
     c->scene_ready = true;

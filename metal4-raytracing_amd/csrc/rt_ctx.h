@@ -1,6 +1,7 @@
 // rt_ctx.h — the context behind the C ABI (include/rt_api.h) and what the files that implement
 // it share: rt_api.cpp (create / destroy, setters, statistics), rt_api_scene.cpp (scene, BVH,
-// geometry updates), rt_api_frame.cpp (frames, reads, tiles, present).  Internal.
+// geometry updates), rt_api_frame.cpp (frames, reads, tiles, present), rt_api_query.cpp (device
+// ray queries).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,6 +60,19 @@ struct Geo {
     uint32_t num_nodes8 = 0;
     rt::DevBuf& operator[](Buf b) { return buf[b]; }
     const rt::DevBuf& operator[](Buf b) const { return buf[b]; }
+};
+
+// One device ray query in flight (rt_trace_closest / rt_trace_any): the launch's own device state
+// (chunk counters and statistics, rt_kernels.h RqParams::state), its pinned copy and its events.
+// Queries rotate over kQuerySlots of these, so launches that may overlap (other streams) share no
+// counter; a slot is reused once its previous query has finished (harvest_query).
+constexpr int kQuerySlots = 4;
+struct QuerySlot {
+    rt::DevBuf state;
+    rt::Pinned<unsigned long long> h_counters;
+    rt::Event ev0, ev1, done;   // around the launch (timing); after the counters' copy
+    bool pending = false, any = false;
+    uint32_t blocks = 0;        // the launch's grid
 };
 
 struct rt_ctx {
@@ -134,6 +148,14 @@ struct rt_ctx {
     int max_in_flight = 0;           // rt_opts.frames_in_flight; 0 = by frame size (wf_in_flight)
     rt::Event scene_ev;              // ctx->stream work a slot-1.. frame must follow
 
+    // device ray queries (rt_api_query.cpp)
+    QuerySlot qslot[kQuerySlots];
+    int qnext = 0;                   // the slot the next query takes (the oldest)
+    rt::DevBuf d_sub_first;          // first scene-wide triangle id per [mesh * max_sub + submesh]
+    rt::Event q_uev;                 // the update stream's state a query's stream waits for
+    rt_query_stats qstats{};
+    bool q_overflow = false;         // a harvested query overflowed its stack: reported by rt_wait / rt_get_query_stats
+
     // motion bookkeeping for the extra-sample pass: motion vectors are exactly zero unless the
     // camera, an instance transform or skinned positions differ from their previous copies
     bool inst_moved = false, skin_moved = false, last_moving = false;
@@ -167,5 +189,9 @@ inline void dev_free(rt_ctx* c, rt::DevBuf& b) { b.release(c->dev_bytes); }
 int refit_rebuild_pct(const rt_ctx* c);   // rt_tuning.refit_rebuild_pct with its default
 // rt_api_frame.cpp: waits for every frame in flight
 rt_status drain_frames(rt_ctx* c);
+// rt_api_query.cpp: waits for every pending query and folds it into rt_query_stats, oldest first.
+// Everything that writes geometry or the tree calls it first, so no query races an update of the
+// generation it reads; rt_wait and rt_get_query_stats report a stack overflow it found.
+rt_status drain_queries(rt_ctx* c);
 // rt_api_scene.cpp: rebuilds the tree once a refit has degraded it (before a refit or a frame)
 rt_status check_refit_quality(rt_ctx* c, bool* rebuilt);

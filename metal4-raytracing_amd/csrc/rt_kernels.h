@@ -118,6 +118,27 @@ size_t lbvh_scratch_bytes(uint32_t n);
 bool lbvh_build(const LbvhInput& in, const LbvhOutput& out, void* scratch, hipStream_t s, LbvhResult* res,
                 const char** err);
 
+// Device ray queries (rt_query.hip): one persistent launch of rq_trace over a flat array of n
+// caller rays (two 16-B words each: origin, direction + tmax).  `state` is the launch's own device
+// block, zeroed before it: the statistics counters (kCounterWords, block_flush_counters' layout:
+// kCntClosest / kCntShadow rays, kCntPaths rays that hit / are occluded, nodes, triangles,
+// overflow), then kRqChunkCounters chunk counters, one per 128-B line.
+constexpr int kRqChunk = 64;          // rays per chunk grab
+constexpr int kRqChunkCounters = 8;   // one per XCD (blockIdx % 8)
+constexpr size_t kRqStateBytes = sizeof(unsigned long long) * kCounterWords + 128 * kRqChunkCounters;
+struct RqParams {
+    const float4* rays;
+    float4* hits;               // closest hit: two 16-B words per ray (rt_ray_hit)
+    uint32_t* occluded;         // any hit: one word per ray
+    const uint32_t* sub_first;  // first scene-wide triangle id of submesh [mesh * max_submeshes + submesh]
+    unsigned long long* state;
+    uint32_t n;
+    int refill_min;
+};
+// resident blocks (CUs x blocks per CU) of the query kernels
+unsigned query_resident_blocks();
+void launch_query(const DevScene& S, const RqParams& Q, bool any, bool count, unsigned blocks, hipStream_t stream);
+
 // Utility kernels (rt_util.hip)
 // G-buffer-guided denoise for RT_SCALER_DENOISED (rt_present.hip); returns tmp0 or tmp1, whichever
 // holds the result (passes = 0 returns the demodulated radiance unremodulated: callers pass >= 1)

@@ -1,0 +1,198 @@
+"""Device ray queries against the renderer's own primary-ray traversal: one JSON
+line for C3g at 1920x1080.
+
+(a) frame: one frame with debugTextureMode = 1 and samplesPerPixel = 4, graphs off, one frame in
+    flight, tail_paths = 1, so that only primary rays are traced, all of them by the extend launch:
+    rate = trace_closest_rays / kernel_ms[1].  Reported only if closest_rays == W * H * 4.
+(b) query: Renderer.trace on W * H * 4 rays through the pixel centres of camera_default (four per
+    pixel; pixels in the frame's order, 64-pixel tiles and Morton order within a tile):
+    rate = rays / query_stats().device_ms.
+
+Each is the median of five runs after two warm-up runs, in a child process of its own whose
+every run has a time limit (the child is killed when a run does not report in time).  After the
+timed runs each child does one counting run for the node visits and triangle tests per ray.
+
+    python tools/query_bench.py [--scene c3g] [--width 1920] [--height 1080] [--run-timeout 60]
+"""
+import argparse
+import importlib
+import json
+import os
+import selectors
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WARMUP, RUNS = 2, 5
+
+
+def _rt():
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    return importlib.import_module("metal4-raytracing_amd")
+
+
+def _emit(**kw):
+    print(json.dumps(kw), flush=True)
+
+
+def child_frame(args):
+    rt = _rt()
+    W, H = args.width, args.height
+    R = rt.Renderer(rt.Scene.preset(args.scene), W, H, tail_paths=1, frames_in_flight=1)
+    R.set_graphs(False)
+    R.debugTextureMode = 1
+    R.samplesPerPixel = 4
+    _emit(ready=True)
+    for k in range(WARMUP + RUNS + 1):
+        counting = k == WARMUP + RUNS
+        R.set_counting(counting)
+        R.draw()
+        s = R.stats()
+        if s.closest_rays != W * H * 4 or s.trace_closest_rays != W * H * 4 or s.shadow_rays != 0:
+            _emit(error=f"the frame traced {s.closest_rays} closest-hit rays ({s.trace_closest_rays} by the extend "
+                        f"launch) and {s.shadow_rays} shadow rays, not {W * H * 4} primary rays only")
+            return 1
+        if counting:
+            _emit(counting=True, nodes_per_ray=s.trace_nodes / s.trace_rays, tris_per_ray=s.trace_tris / s.trace_rays)
+        elif not s.kernel_ms[1] > 0:
+            _emit(error="the frame recorded no extend time (kernel_ms[1])")
+            return 1
+        else:
+            _emit(run=k, rays=int(s.trace_closest_rays), ms=float(s.kernel_ms[1]))
+    R.close()
+    return 0
+
+
+def camera_rays(rt, W, H, device):
+    """(W * H * 4, 8) rays through the pixel centres of camera_default, as the kernels form them
+    (generate_ray, rt_shade.h), four per pixel, pixels in the frame's order."""
+    import numpy as np
+    import torch
+    ys, xs = np.mgrid[0:H, 0:W]
+    tile = (ys // 64) * ((W + 63) // 64) + xs // 64
+    lx, ly = (xs % 64).astype(np.uint32), (ys % 64).astype(np.uint32)
+    morton = np.zeros_like(lx)
+    for b in range(6):
+        morton |= ((lx >> b) & 1) << (2 * b) | ((ly >> b) & 1) << (2 * b + 1)
+    order = np.lexsort((morton.ravel(), tile.ravel()))
+    px = torch.from_numpy(xs.ravel()[order].astype(np.float32)).to(device)
+    py = torch.from_numpy(ys.ravel()[order].astype(np.float32)).to(device)
+    cam = rt.camera_default(W, H)
+    v = lambda f: torch.tensor(f.tolist(), dtype=torch.float32, device=device)
+    ux = (px + 0.5) / W * 2.0 - 1.0
+    uy = (py + 0.5) / H * 2.0 - 1.0
+    d = ux[:, None] * v(cam.right) + uy[:, None] * v(cam.up) + v(cam.forward)
+    d = d / d.norm(dim=1, keepdim=True)
+    o = v(cam.position).expand_as(d)
+    rays = rt.Renderer.make_rays(o, d)
+    return rays.repeat_interleave(4, dim=0).contiguous()
+
+
+def child_query(args):
+    rt = _rt()
+    import torch
+    W, H = args.width, args.height
+    R = rt.Renderer(rt.Scene.preset(args.scene), 64, 64)
+    rays = camera_rays(rt, W, H, torch.device("cuda", 0))
+    out = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
+    torch.cuda.synchronize()
+    _emit(ready=True)
+    for k in range(WARMUP + RUNS + 1):
+        counting = k == WARMUP + RUNS
+        R.set_counting(counting)
+        R.trace(rays, out=out)
+        q = R.query_stats()
+        if counting:
+            _emit(counting=True, nodes_per_ray=q.node_visits / q.rays, tris_per_ray=q.tri_tests / q.rays)
+        else:
+            _emit(run=k, rays=int(q.rays), ms=float(q.device_ms), hits=int(q.hits), grid_blocks=int(q.grid_blocks))
+    R.close()
+    return 0
+
+
+def run_child(kind, args):
+    """The child's reports; every line has to arrive within its time limit."""
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--scene", args.scene, "--width", str(args.width),
+           "--height", str(args.height)]
+    p = subprocess.Popen(cmd, stdout=subprocess.PIPE)
+    fd = p.stdout.fileno()
+    sel = selectors.DefaultSelector()
+    sel.register(fd, selectors.EVENT_READ)
+    lines, limit = [], args.setup_timeout   # the first report follows the scene load and the BVH build
+    buf = b""
+    try:
+        while True:
+            while b"\n" not in buf:
+                if not sel.select(timeout=limit):
+                    p.kill()
+                    return lines, f"{kind}: no report within {limit} s; child killed"
+                chunk = os.read(fd, 65536)
+                if not chunk:
+                    break
+                buf += chunk
+            if b"\n" not in buf:
+                break   # end of the child's output
+            line, buf = buf.split(b"\n", 1)
+            rec = json.loads(line)
+            if "error" in rec:
+                return lines, f"{kind}: {rec['error']}"
+            lines.append(rec)
+            limit = args.run_timeout
+    finally:
+        sel.close()
+        if p.poll() is None:
+            try:
+                p.wait(timeout=args.run_timeout)
+            except subprocess.TimeoutExpired:
+                p.kill()
+    if p.returncode != 0:
+        return lines, f"{kind}: child exited with status {p.returncode}"
+    return lines, None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", default="c3g")
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--run-timeout", type=float, default=60.0, help="seconds each run may take")
+    ap.add_argument("--setup-timeout", type=float, default=240.0, help="seconds the scene load and BVH build may take")
+    ap.add_argument("--child", choices=["frame", "query"])
+    args = ap.parse_args()
+    if args.child:
+        return (child_frame if args.child == "frame" else child_query)(args)
+    res = {"scene": args.scene, "width": args.width, "height": args.height, "rays": args.width * args.height * 4}
+    for kind in ("frame", "query"):
+        t0 = time.time()
+        lines, err = run_child(kind, args)
+        if err:
+            res["error"] = err
+            print(json.dumps(res))
+            return 1
+        runs = [r for r in lines if "run" in r and r["run"] >= WARMUP]
+        if len(runs) != RUNS:
+            res["error"] = f"{kind}: {len(runs)} timed runs reported, not {RUNS}"
+            print(json.dumps(res))
+            return 1
+        rates = [r["rays"] / r["ms"] * 1e-6 for r in runs]   # rays / ms -> Grays/s
+        res[f"{kind}_grays"] = statistics.median(rates)
+        res[f"{kind}_runs_grays"] = [round(x, 4) for x in rates]
+        res[f"{kind}_ms"] = statistics.median(r["ms"] for r in runs)
+        for r in lines:
+            if r.get("counting"):
+                res[f"{kind}_nodes_per_ray"] = round(r["nodes_per_ray"], 3)
+                res[f"{kind}_tris_per_ray"] = round(r["tris_per_ray"], 3)
+        if kind == "query":
+            res["query_hits"] = runs[-1]["hits"]
+            res["query_grid_blocks"] = runs[-1]["grid_blocks"]
+        res[f"{kind}_wall_s"] = round(time.time() - t0, 1)
+    res["ratio"] = res["query_grays"] / res["frame_grays"]
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
