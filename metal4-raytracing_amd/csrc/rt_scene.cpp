@@ -1,711 +1,22 @@
-// rt_scene.cpp — host scene ingest (C++ mirror of the reference's Swift scene layer).
-//
-//   class Scene      ~ MetalRaytracing/Scene.swift:10-170 (lights, orbit camera)
-//   class Model      ~ MetalRaytracing/Model.swift:29-205 (OBJ path, T*R*S transform, overrides)
-//   struct Mesh      ~ MetalRaytracing/Mesh.swift:17-68   (one MDLMesh = one instance)
-//   struct Submesh   ~ MetalRaytracing/SubMesh.swift:18-324 (material group, u32 indices)
-//
-// OBJ/MTL ingest restates the ModelIO conventions the reference relies on:
-// one mesh per `o` object, one submesh per material (first-appearance order), one vertex per
-// unique (v, vt, vn) tuple, fan triangulation of polygons, normals left zero when the file has
-// no `vn` (Raytracing.metal:395-397 then falls back to -ray.direction), Kd->baseColor,
-// Ks->specular, Ke->emission, Ni->refractionIndex (default 1), d->opacity (default 1, clamped),
-// specularExponent left 0 (Material(material:) only reads it for a float3 property,
-// SubMesh.swift:309-311).  ModelIO itself is unvendored: its exact triangulation/dedup order
-// is parity-unpinned and documented in DESIGN.md.
-#include "../../include/rt_scene.h"
-#include "rt_usd.h"
+// rt_scene.cpp — the rt_scene_* C entry points over the in-memory scene (rt_scene_model.h): scene
+// lifetime, the readers as thin guarded calls, the texture registry, presets (AppScene.swift:14-28),
+// the flattened description, lights and the orbit camera (Scene.swift:10-170), default uniforms and
+// random offsets.  The readers are rt_scene_obj.cpp, rt_scene_procedural.cpp and rt_scene_usd.cpp.
+#include "rt_scene_model.h"
+#include "rt_file.h"
 
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <climits>
-#include <cstdint>
-#include <functional>
-#include <map>
-#include <memory>
-#include <tuple>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-namespace rt {
-
-// ---- column-major float4x4 helpers (Utilities.swift:302-355) --------------------------------
-struct M4 { float m[16]; };  // m[col*4 + row]
-
-static M4 m4_identity() { M4 r{}; r.m[0] = r.m[5] = r.m[10] = r.m[15] = 1.0f; return r; }
-static M4 m4_mul(const M4& a, const M4& b) {
-    M4 r{};
-    for (int c = 0; c < 4; ++c)
-        for (int rr = 0; rr < 4; ++rr) {
-            float s = 0.0f;
-            for (int k = 0; k < 4; ++k) s = s + a.m[k * 4 + rr] * b.m[c * 4 + k];
-            r.m[c * 4 + rr] = s;
-        }
-    return r;
-}
-static M4 m4_translate(const float t[3]) { M4 r = m4_identity(); r.m[12] = t[0]; r.m[13] = t[1]; r.m[14] = t[2]; return r; }
-static M4 m4_scale(float s) { M4 r = m4_identity(); r.m[0] = s; r.m[5] = s; r.m[10] = s; return r; }
-// matrix_float4x4.rotate(radians:axis:) (Utilities.swift:318-331)
-static M4 m4_rotate_axis(float radians, float ax, float ay, float az) {
-    float len = std::sqrt(ax * ax + ay * ay + az * az);
-    float x = ax / len, y = ay / len, z = az / len;
-    float ct = cosf(radians), st = sinf(radians), ci = 1.0f - ct;
-    M4 r{};
-    r.m[0] = ct + x * x * ci;     r.m[1] = y * x * ci + z * st; r.m[2] = z * x * ci - y * st;  r.m[3] = 0;
-    r.m[4] = x * y * ci - z * st; r.m[5] = ct + y * y * ci;     r.m[6] = z * y * ci + x * st;  r.m[7] = 0;
-    r.m[8] = x * z * ci + y * st; r.m[9] = y * z * ci - x * st; r.m[10] = ct + z * z * ci;     r.m[11] = 0;
-    r.m[12] = 0; r.m[13] = 0; r.m[14] = 0; r.m[15] = 1;
-    return r;
-}
-// rotate(r) = rotateX(r.x) * rotateY(r.y) * rotateZ(r.z) (Utilities.swift:345-347)
-static M4 m4_rotate(const float r[3]) {
-    return m4_mul(m4_mul(m4_rotate_axis(r[0], 1, 0, 0), m4_rotate_axis(r[1], 0, 1, 0)), m4_rotate_axis(r[2], 0, 0, 1));
-}
-// worldTransform = T * R * S (Model.swift:55-58, Mesh.swift:61-66)
-static M4 model_transform(const float pos[3], const float rot[3], float scale) {
-    return m4_mul(m4_mul(m4_translate(pos), m4_rotate(rot)), m4_scale(scale));
-}
-static rt_packed_float4x3 pack4x3(const M4& a) {  // Renderer.swift:1393-1401
-    rt_packed_float4x3 p;
-    for (int c = 0; c < 4; ++c)
-        for (int r = 0; r < 3; ++r) p.columns[c][r] = a.m[c * 4 + r];
-    return p;
-}
-
-static rt_float3 f3(float x, float y, float z) { rt_float3 v; v.x = x; v.y = y; v.z = z; v._pad = 0.0f; return v; }
-
-struct Submesh {
-    std::string material_name;
-    std::vector<uint32_t> indices;
-    Material material;
-    int32_t tex[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // scene texture per slot (RT_TEXTURE_SLOTS)
-    std::string tex_path[RT_TEXTURE_SLOTS];                // MTL maps, bound by rt_scene_add_obj
-};
-
-// MTL map statements -> texture slot (ModelIO's material semantics, SubMesh.swift:117-166)
-static int map_slot(const char* key) {
-    static const struct { const char* k; int slot; } kMaps[] = {
-        {"map_Kd", 0}, {"norm", 1}, {"bump", 1}, {"map_Bump", 1}, {"map_bump", 1}, {"map_Pr", 2},
-        {"map_Pm", 3}, {"map_Ke", 5}, {"map_d", 6}};
-    for (const auto& m : kMaps)
-        if (!std::strcmp(key, m.k)) return m.slot;
-    return -1;
-}
-struct MtlEntry {
-    Material material;
-    std::string maps[RT_TEXTURE_SLOTS];
-};
-
-struct Skin {
-    // Synthetic skeleton for the robot stand-in (config 5): a chain of joints along +Y.
-    std::vector<int> parent;
-    std::vector<M4> rest_local;      // local rest transforms
-    std::vector<M4> inverse_bind;    // inverse of global bind transforms
-    double duration = 2.0;
-};
-
-// Model.skeleton / Model.animation of a USD asset (Model.swift:346-414): joint paths, parents
-// from the paths, rest transforms, inverse bind transforms, and the packed joint animation as
-// keyframe tracks (time in seconds, translations / rotations (x, y, z, w) / scales per joint).
-struct UsdSkel {
-    std::vector<std::string> joint_paths;
-    std::vector<int> parent;
-    std::vector<M4> rest, inverse_bind;
-    struct Track {
-        int comps = 3;
-        std::vector<double> t;
-        std::vector<std::vector<float>> v;   // per key: comps * joints
-    };
-    bool has_anim = false;
-    std::vector<std::string> anim_paths;
-    Track tr, rot, sc;
-    double duration = 0.0;
-};
-
-struct Mesh {
-    std::string name;
-    std::vector<rt_float3> positions, normals;
-    std::vector<rt_float2> uvs;
-    bool has_uvs = false;
-    std::vector<uint16_t> joint_indices;  // ushort4 per vertex
-    std::vector<float> joint_weights;     // float4 per vertex
-    std::vector<Submesh> submeshes;
-    M4 transform;
-    uint32_t joint_count = 0;
-    std::shared_ptr<Skin> skin;
-    // USD skinning (MeshSkinningInfo, Mesh.swift:10-15): the model's skeleton, this mesh's joint
-    // order mapped to skeleton indices, geometryBindTransform and its inverse
-    std::shared_ptr<UsdSkel> usd_skel;
-    std::vector<int> joint_to_skel;
-    M4 geom_bind, geom_bind_inv;
-};
-
-struct Model {
-    std::string name;
-    float position[3], rotation[3], scale;
-    std::vector<Mesh> meshes;
-};
-
-static Material default_material() {
-    Material m;
-    std::memset(&m, 0, sizeof(m));
-    m.refractionIndex = 1.0f;   // SubMesh.swift:295-296
-    m.opacity = 1.0f;
-    m.textureFlags = 0;
-    return m;
-}
-
-// ModelMaterialOverride application (SubMesh.swift:272-288)
-static void apply_override(Material& m, const rt_material_override* ov) {
-    if (!ov) return;
-    if (ov->has_base_color) m.baseColor = f3(ov->base_color[0], ov->base_color[1], ov->base_color[2]);
-    if (ov->has_refraction_index) m.refractionIndex = std::max(ov->refraction_index, 1.0f);
-    if (ov->has_opacity) m.opacity = std::min(std::max(ov->opacity, 0.0f), 1.0f);
-}
-
-static std::string dir_of(const std::string& p) {
-    size_t s = p.find_last_of('/');
-    return s == std::string::npos ? std::string(".") : p.substr(0, s);
-}
-
-// ---- MTL -------------------------------------------------------------------------------------
-static bool parse_mtl(const std::string& path, std::map<std::string, MtlEntry>& out) {
-    FILE* f = std::fopen(path.c_str(), "r");
-    if (!f) return false;
-    char line[4096];
-    MtlEntry* ent = nullptr;
-    while (std::fgets(line, sizeof line, f)) {
-        char* p = line;
-        while (*p == ' ' || *p == '\t') ++p;
-        char key[64] = {0};
-        int n = 0;
-        if (std::sscanf(p, "%63s%n", key, &n) != 1) continue;
-        const char* rest = p + n;
-        if (!std::strcmp(key, "newmtl")) {
-            char name[1024] = {0};
-            std::sscanf(rest, " %1023[^\r\n]", name);
-            out[name].material = default_material();
-            ent = &out[name];
-        } else if (ent) {
-            Material* cur = &ent->material;
-            const int slot = map_slot(key);
-            if (slot >= 0) {   // the file name is the statement's last token (options come first)
-                std::string r(rest);
-                while (!r.empty() && (r.back() == '\n' || r.back() == '\r' || r.back() == ' ' || r.back() == '\t'))
-                    r.pop_back();
-                size_t sp = r.find_last_of(" \t");
-                std::string file = sp == std::string::npos ? r : r.substr(sp + 1);
-                if (!file.empty()) ent->maps[slot] = file[0] == '/' ? file : dir_of(path) + "/" + file;
-                continue;
-            }
-            float a = 0, b = 0, c = 0;
-            int k = std::sscanf(rest, "%f %f %f", &a, &b, &c);
-            if (!std::strcmp(key, "Kd") && k >= 3) cur->baseColor = f3(a, b, c);
-            else if (!std::strcmp(key, "Ks") && k >= 3) cur->specular = f3(a, b, c);
-            else if (!std::strcmp(key, "Ke") && k >= 3) cur->emission = f3(a, b, c);
-            else if (!std::strcmp(key, "Ni") && k >= 1) cur->refractionIndex = a;
-            else if (!std::strcmp(key, "d") && k >= 1) cur->opacity = std::min(std::max(a, 0.0f), 1.0f);
-            else if (!std::strcmp(key, "Tr") && k >= 1) cur->opacity = std::min(std::max(1.0f - a, 0.0f), 1.0f);
-        }
-    }
-    std::fclose(f);
-    return true;
-}
-
-// ---- OBJ -------------------------------------------------------------------------------------
-struct ObjKey {
-    int v, t, n;
-    bool operator==(const ObjKey& o) const { return v == o.v && t == o.t && n == o.n; }
-};
-struct ObjKeyHash {
-    size_t operator()(const ObjKey& k) const {
-        return (size_t)k.v * 73856093u ^ (size_t)k.t * 19349663u ^ (size_t)k.n * 83492791u;
-    }
-};
-
-static bool load_obj(const std::string& path, std::vector<Mesh>& meshes, std::string& err) {
-    FILE* f = std::fopen(path.c_str(), "r");
-    if (!f) { err = "cannot open " + path; return false; }
-    std::vector<float> V, VT, VN;
-    std::map<std::string, MtlEntry> mtl;
-    Mesh* mesh = nullptr;
-    std::unordered_map<ObjKey, uint32_t, ObjKeyHash> dedup;
-    std::map<std::string, size_t> sub_of;
-    size_t cur_sub = (size_t)-1;
-    std::string cur_mtl = "";
-    auto start_mesh = [&](const std::string& name) {
-        meshes.emplace_back();
-        mesh = &meshes.back();
-        mesh->name = name;
-        mesh->transform = m4_identity();
-        dedup.clear();
-        sub_of.clear();
-        cur_sub = (size_t)-1;
-    };
-    auto select_sub = [&]() {
-        if (!mesh) start_mesh("default");
-        auto it = sub_of.find(cur_mtl);
-        if (it == sub_of.end()) {
-            Submesh s;
-            s.material_name = cur_mtl;
-            auto mi = mtl.find(cur_mtl);
-            s.material = (mi != mtl.end()) ? mi->second.material : default_material();
-            if (mi != mtl.end())
-                for (int k = 0; k < RT_TEXTURE_SLOTS; ++k) s.tex_path[k] = mi->second.maps[k];
-            mesh->submeshes.push_back(s);
-            cur_sub = mesh->submeshes.size() - 1;
-            sub_of[cur_mtl] = cur_sub;
-        } else {
-            cur_sub = it->second;
-        }
-    };
-    char line[1 << 14];
-    std::vector<uint32_t> poly;
-    while (std::fgets(line, sizeof line, f)) {
-        char* p = line;
-        while (*p == ' ' || *p == '\t') ++p;
-        if (p[0] == 'v' && p[1] == ' ') {
-            float x = 0, y = 0, z = 0;
-            std::sscanf(p + 2, "%f %f %f", &x, &y, &z);
-            V.push_back(x); V.push_back(y); V.push_back(z);
-        } else if (p[0] == 'v' && p[1] == 't') {
-            float x = 0, y = 0;
-            std::sscanf(p + 2, "%f %f", &x, &y);
-            VT.push_back(x); VT.push_back(y);
-        } else if (p[0] == 'v' && p[1] == 'n') {
-            float x = 0, y = 0, z = 0;
-            std::sscanf(p + 2, "%f %f %f", &x, &y, &z);
-            VN.push_back(x); VN.push_back(y); VN.push_back(z);
-        } else if (p[0] == 'o' && (p[1] == ' ' || p[1] == '\t')) {
-            char name[1024] = {0};
-            std::sscanf(p + 1, " %1023[^\r\n]", name);
-            start_mesh(name);
-        } else if (!std::strncmp(p, "mtllib", 6)) {
-            char name[1024] = {0};
-            std::sscanf(p + 6, " %1023[^\r\n]", name);
-            parse_mtl(dir_of(path) + "/" + name, mtl);
-        } else if (!std::strncmp(p, "usemtl", 6)) {
-            char name[1024] = {0};
-            std::sscanf(p + 6, " %1023[^\r\n]", name);
-            cur_mtl = name;
-            cur_sub = (size_t)-1;
-        } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
-            if (!mesh) start_mesh("default");
-            if (cur_sub == (size_t)-1) select_sub();
-            poly.clear();
-            char* q = p + 1;
-            while (*q) {
-                while (*q == ' ' || *q == '\t') ++q;
-                if (!*q || *q == '\n' || *q == '\r') break;
-                int vi = 0, ti = 0, ni = 0;
-                vi = (int)std::strtol(q, &q, 10);
-                if (*q == '/') {
-                    ++q;
-                    if (*q != '/') ti = (int)std::strtol(q, &q, 10);
-                    if (*q == '/') { ++q; ni = (int)std::strtol(q, &q, 10); }
-                }
-                while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') ++q;
-                int nv = (int)V.size() / 3, nt = (int)VT.size() / 2, nn = (int)VN.size() / 3;
-                if (vi < 0) vi = nv + vi + 1;
-                if (ti < 0) ti = nt + ti + 1;
-                if (ni < 0) ni = nn + ni + 1;
-                if (vi <= 0 || vi > nv || ti > nt || ni > nn) { err = "bad face index in " + path; std::fclose(f); return false; }
-                ObjKey key{vi, ti, ni};
-                auto it = dedup.find(key);
-                uint32_t idx;
-                if (it == dedup.end()) {
-                    idx = (uint32_t)mesh->positions.size();
-                    dedup.emplace(key, idx);
-                    mesh->positions.push_back(f3(V[3 * (vi - 1)], V[3 * (vi - 1) + 1], V[3 * (vi - 1) + 2]));
-                    mesh->normals.push_back(ni > 0 ? f3(VN[3 * (ni - 1)], VN[3 * (ni - 1) + 1], VN[3 * (ni - 1) + 2]) : f3(0, 0, 0));
-                    rt_float2 uv; uv.x = 0; uv.y = 0;
-                    if (ti > 0) { uv.x = VT[2 * (ti - 1)]; uv.y = VT[2 * (ti - 1) + 1]; mesh->has_uvs = true; }
-                    mesh->uvs.push_back(uv);
-                } else {
-                    idx = it->second;
-                }
-                poly.push_back(idx);
-            }
-            auto& ind = mesh->submeshes[cur_sub].indices;
-            for (size_t k = 2; k < poly.size(); ++k) {  // fan triangulation
-                ind.push_back(poly[0]); ind.push_back(poly[k - 1]); ind.push_back(poly[k]);
-            }
-        }
-    }
-    std::fclose(f);
-    // drop empty submeshes / meshes
-    for (auto& m : meshes) {
-        std::vector<Submesh> keep;
-        for (auto& s : m.submeshes) if (!s.indices.empty()) keep.push_back(std::move(s));
-        m.submeshes.swap(keep);
-    }
-    std::vector<Mesh> keepm;
-    for (auto& m : meshes) if (!m.submeshes.empty()) keepm.push_back(std::move(m));
-    meshes.swap(keepm);
-    if (meshes.empty()) { err = "no faces in " + path; return false; }
-    return true;
-}
-
-// ---- procedural stand-ins ----------------------------------------------------------------------
-static void compute_vertex_normals(Mesh& m) {
-    std::vector<double> acc(m.positions.size() * 3, 0.0);
-    for (auto& s : m.submeshes)
-        for (size_t t = 0; t + 2 < s.indices.size(); t += 3) {
-            const rt_float3& a = m.positions[s.indices[t]];
-            const rt_float3& b = m.positions[s.indices[t + 1]];
-            const rt_float3& c = m.positions[s.indices[t + 2]];
-            double e1[3] = {(double)b.x - a.x, (double)b.y - a.y, (double)b.z - a.z};
-            double e2[3] = {(double)c.x - a.x, (double)c.y - a.y, (double)c.z - a.z};
-            double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-            for (int k = 0; k < 3; ++k)
-                for (int j = 0; j < 3; ++j) acc[3 * s.indices[t + k] + j] += n[j];
-        }
-    m.normals.resize(m.positions.size());
-    for (size_t i = 0; i < m.positions.size(); ++i) {
-        double* n = &acc[3 * i];
-        double l = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-        if (l > 0) m.normals[i] = f3((float)(n[0] / l), (float)(n[1] / l), (float)(n[2] / l));
-        else m.normals[i] = f3(0, 0, 0);
-    }
-}
-
-// Fit positions into the box [-h, h] per axis (centred), preserving nothing else.
-static void fit_box(Mesh& m, const double half[3]) {
-    double lo[3] = {1e30, 1e30, 1e30}, hi[3] = {-1e30, -1e30, -1e30};
-    for (auto& p : m.positions) {
-        double v[3] = {p.x, p.y, p.z};
-        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], v[k]); hi[k] = std::max(hi[k], v[k]); }
-    }
-    for (auto& p : m.positions) {
-        double v[3] = {p.x, p.y, p.z};
-        for (int k = 0; k < 3; ++k) {
-            double c = 0.5 * (lo[k] + hi[k]), e = 0.5 * (hi[k] - lo[k]);
-            v[k] = (v[k] - c) / e * half[k];
-        }
-        p = f3((float)v[0], (float)v[1], (float)v[2]);
-    }
-}
-
-// Closed tube of U x V quads around a (2,3) torus knot with bumps: 2*U*V triangles.
-// dragon: U=10627, V=41 -> 871,414 triangles, the triangle count of the Stanford dragon
-// asset named by BASELINE.json; bounds ~ (0.45, 0.317, 0.2) half-extents so that at the
-// AppScene transform (scale 1.2 at y=0.38, AppScene.swift:16-21) it rests on the floor.
-static Mesh make_knot(const char* name, int U, int V, double tube, double bump, const double half[3]) {
-    Mesh m;
-    m.name = name;
-    m.transform = m4_identity();
-    m.positions.reserve((size_t)U * V);
-    const double TWO_PI = 6.283185307179586;
-    for (int i = 0; i < U; ++i) {
-        double t = TWO_PI * i / U;
-        // trefoil knot and its derivative
-        double cx = std::sin(t) + 2.0 * std::sin(2 * t), cy = std::cos(t) - 2.0 * std::cos(2 * t), cz = -std::sin(3 * t);
-        double dx = std::cos(t) + 4.0 * std::cos(2 * t), dy = -std::sin(t) + 4.0 * std::sin(2 * t), dz = -3.0 * std::cos(3 * t);
-        double dl = std::sqrt(dx * dx + dy * dy + dz * dz);
-        dx /= dl; dy /= dl; dz /= dl;
-        // B = normalize(T x Z), N = B x T
-        double bx = dy * 1.0 - dz * 0.0, by = dz * 0.0 - dx * 1.0, bz = 0.0;
-        double bl = std::sqrt(bx * bx + by * by + bz * bz);
-        bx /= bl; by /= bl; bz /= bl;
-        double nx = by * dz - bz * dy, ny = bz * dx - bx * dz, nz = bx * dy - by * dx;
-        for (int j = 0; j < V; ++j) {
-            double ph = TWO_PI * j / V;
-            double r = tube * (1.0 + bump * std::sin(13.0 * t + 3.0 * ph) * std::cos(7.0 * t - 2.0 * ph)
-                               + 0.5 * bump * std::sin(57.0 * t + 5.0 * ph));
-            double px = cx + r * (std::cos(ph) * nx + std::sin(ph) * bx);
-            double py = cy + r * (std::cos(ph) * ny + std::sin(ph) * by);
-            double pz = cz + r * (std::cos(ph) * nz + std::sin(ph) * bz);
-            m.positions.push_back(f3((float)px, (float)py, (float)pz));
-        }
-    }
-    Submesh s;
-    s.indices.reserve((size_t)U * V * 6);
-    for (int i = 0; i < U; ++i) {
-        int i1 = (i + 1) % U;
-        for (int j = 0; j < V; ++j) {
-            int j1 = (j + 1) % V;
-            uint32_t a = i * V + j, b = i1 * V + j, c = i1 * V + j1, d = i * V + j1;
-            s.indices.push_back(a); s.indices.push_back(c); s.indices.push_back(b);   // outward winding
-            s.indices.push_back(a); s.indices.push_back(d); s.indices.push_back(c);
-        }
-    }
-    s.material = default_material();
-    m.submeshes.push_back(std::move(s));
-    fit_box(m, half);
-    compute_vertex_normals(m);
-    m.uvs.assign(m.positions.size(), rt_float2{0.0f, 0.0f});
-    return m;
-}
-
-// Append a closed "swept" surface (UV-sphere topology, poles at both ends) around a spine:
-// 2 * U * (R - 1) triangles.  point(s, phi) = C(s) + r(s, phi) * (cos phi N + sin phi B).
-template <class Spine, class Radius>
-static void append_swept(Mesh& m, int U, int R, Spine spine, Radius radius) {
-    const double PI = 3.141592653589793;
-    uint32_t base = (uint32_t)m.positions.size();
-    double c[3], t[3];
-    auto frame = [&](double s, double* C, double* N, double* B) {
-        double h = 1e-4, a[3], b[3];
-        spine(s, C);
-        spine(std::min(1.0, s + h), a);
-        spine(std::max(0.0, s - h), b);
-        double T[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-        double tl = std::sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]);
-        for (double& v : T) v /= tl;
-        B[0] = T[1]; B[1] = -T[0]; B[2] = 0.0;  // T x Z
-        double bl = std::sqrt(B[0] * B[0] + B[1] * B[1]);
-        B[0] /= bl; B[1] /= bl;
-        N[0] = B[1] * T[2] - B[2] * T[1];
-        N[1] = B[2] * T[0] - B[0] * T[2];
-        N[2] = B[0] * T[1] - B[1] * T[0];
-    };
-    spine(0.0, c);
-    m.positions.push_back(f3((float)c[0], (float)c[1], (float)c[2]));
-    for (int r = 1; r < R; ++r) {
-        double s = (double)r / R, C[3], N[3], B[3];
-        frame(s, C, N, B);
-        for (int u = 0; u < U; ++u) {
-            double ph = 2 * PI * u / U;
-            double rr = radius(s, ph);
-            m.positions.push_back(f3((float)(C[0] + rr * (std::cos(ph) * N[0] + std::sin(ph) * B[0])),
-                                     (float)(C[1] + rr * (std::cos(ph) * N[1] + std::sin(ph) * B[1])),
-                                     (float)(C[2] + rr * (std::cos(ph) * N[2] + std::sin(ph) * B[2]))));
-        }
-    }
-    spine(1.0, t);
-    m.positions.push_back(f3((float)t[0], (float)t[1], (float)t[2]));
-    uint32_t south = (uint32_t)m.positions.size() - 1;
-    auto& ind = m.submeshes[0].indices;
-    auto ring = [&](int r, int u) -> uint32_t { return base + 1 + (uint32_t)((r - 1) * U + (u % U)); };
-    for (int u = 0; u < U; ++u) { ind.push_back(base); ind.push_back(ring(1, u + 1)); ind.push_back(ring(1, u)); }
-    for (int r = 1; r < R - 1; ++r)
-        for (int u = 0; u < U; ++u) {
-            uint32_t a = ring(r, u), b = ring(r, u + 1), cc = ring(r + 1, u + 1), d = ring(r + 1, u);
-            ind.push_back(a); ind.push_back(b); ind.push_back(cc);
-            ind.push_back(a); ind.push_back(cc); ind.push_back(d);
-        }
-    for (int u = 0; u < U; ++u) { ind.push_back(south); ind.push_back(ring(R - 1, u)); ind.push_back(ring(R - 1, u + 1)); }
-}
-
-// Dragon stand-in: one closed, compact, detailed surface like the Stanford dragon — a curved
-// body swept along an S-shaped spine (thick middle, head bulge, thin tail) with scale-like
-// displacement, plus four legs.  Exactly 871,414 triangles (body 2*560*740 + legs
-// 3*(2*64*83) + 2*41*131); half-extents (0.45, 0.3166, 0.2) so that at the AppScene transform
-// (scale 1.2 at y = 0.38, AppScene.swift:16-21) it rests on the floor.
-static Mesh make_dragon(const double half[3]) {
-    Mesh m;
-    m.name = "dragon";
-    m.transform = m4_identity();
-    m.submeshes.emplace_back();
-    m.submeshes[0].material = default_material();
-    const double PI = 3.141592653589793;
-    auto body_spine = [&](double s, double* C) {
-        C[0] = 2.2 * (s - 0.5);
-        C[1] = 0.30 * std::sin(2 * PI * s + 0.6) + 0.25 * s;
-        C[2] = 0.22 * std::sin(PI * s) * std::sin(3 * PI * s);
-    };
-    auto body_r = [&](double s, double ph) {
-        double r = 0.34 * std::pow(std::sin(PI * s), 0.65) * (1.0 + 0.35 * std::exp(-60.0 * (s - 0.86) * (s - 0.86)));
-        r *= 1.0 + 0.05 * std::sin(90.0 * s + 7.0 * ph) * std::sin(11.0 * ph) + 0.025 * std::sin(310.0 * s) * std::cos(23.0 * ph);
-        return r;
-    };
-    append_swept(m, 560, 741, body_spine, body_r);
-    struct Leg { double s, side; int U, R; };
-    const Leg legs[4] = {{0.32, 1.0, 64, 84}, {0.32, -1.0, 64, 84}, {0.66, 1.0, 64, 84}, {0.66, -1.0, 41, 132}};
-    for (const Leg& L : legs) {
-        double C0[3];
-        body_spine(L.s, C0);
-        auto leg_spine = [&](double s, double* C) {
-            C[0] = C0[0] + 0.08 * s;
-            C[1] = C0[1] - 0.62 * s;
-            C[2] = C0[2] + L.side * (0.10 + 0.12 * s);
-        };
-        auto leg_r = [&](double s, double ph) {
-            return 0.075 * std::pow(std::sin(PI * s), 0.5) * (1.0 + 0.04 * std::sin(40.0 * s + 5.0 * ph));
-        };
-        append_swept(m, L.U, L.R, leg_spine, leg_r);
-    }
-    fit_box(m, half);
-    compute_vertex_normals(m);
-    m.uvs.assign(m.positions.size(), rt_float2{0.0f, 0.0f});
-    return m;
-}
-
-// Lumpy UV sphere: 2*U*(R-1) triangles (bunny stand-in: U=463, R=76 -> 69,450 triangles).
-static Mesh make_blob(const char* name, int U, int R, const double half[3]) {
-    Mesh m;
-    m.name = name;
-    m.transform = m4_identity();
-    const double PI = 3.141592653589793;
-    // rings 1..R-1 plus two poles
-    m.positions.push_back(f3(0, 1, 0));
-    for (int r = 1; r < R; ++r) {
-        double th = PI * r / R;
-        for (int u = 0; u < U; ++u) {
-            double ph = 2 * PI * u / U;
-            double rad = 1.0 + 0.18 * std::sin(3 * th) * std::cos(2 * ph) + 0.07 * std::sin(11 * th + 5 * ph)
-                         + (th < 0.9 ? 0.35 * std::exp(-20.0 * std::pow(std::sin(ph) - 0.6, 2)) * (0.9 - th) : 0.0);
-            m.positions.push_back(f3((float)(rad * std::sin(th) * std::cos(ph)), (float)(rad * std::cos(th)),
-                                     (float)(rad * std::sin(th) * std::sin(ph))));
-        }
-    }
-    m.positions.push_back(f3(0, -1, 0));
-    uint32_t south = (uint32_t)m.positions.size() - 1;
-    Submesh s;
-    auto ring = [&](int r, int u) -> uint32_t { return 1 + (uint32_t)((r - 1) * U + (u % U)); };
-    for (int u = 0; u < U; ++u) { s.indices.push_back(0); s.indices.push_back(ring(1, u + 1)); s.indices.push_back(ring(1, u)); }
-    for (int r = 1; r < R - 1; ++r)
-        for (int u = 0; u < U; ++u) {
-            uint32_t a = ring(r, u), b = ring(r, u + 1), c = ring(r + 1, u + 1), d = ring(r + 1, u);
-            s.indices.push_back(a); s.indices.push_back(b); s.indices.push_back(c);
-            s.indices.push_back(a); s.indices.push_back(c); s.indices.push_back(d);
-        }
-    for (int u = 0; u < U; ++u) { s.indices.push_back(south); s.indices.push_back(ring(R - 1, u)); s.indices.push_back(ring(R - 1, u + 1)); }
-    s.material = default_material();
-    s.material.baseColor = f3(0.8f, 0.8f, 0.8f);
-    m.submeshes.push_back(std::move(s));
-    fit_box(m, half);
-    compute_vertex_normals(m);
-    m.uvs.assign(m.positions.size(), rt_float2{0.0f, 0.0f});
-    return m;
-}
-
-// Skinned robot stand-in (config 5): a segmented capsule "arm" of J joints along +Y whose
-// joints bend about Z over time.  4 joint influences per vertex (Model.swift:304-341 streams).
-static Mesh make_robot(int J, int rings_per_joint, int U) {
-    Mesh m;
-    m.name = "robot";
-    m.transform = m4_identity();
-    const double PI = 3.141592653589793;
-    const double seg = 0.6, radius = 0.18;
-    int R = J * rings_per_joint + 1;
-    for (int r = 0; r < R; ++r) {
-        double y = seg * J * r / (R - 1);
-        double rad = radius * (0.75 + 0.25 * std::cos(2 * PI * r / rings_per_joint));
-        double jf = y / seg;  // joint coordinate
-        int j0 = std::min((int)std::floor(jf - 0.5), J - 1);
-        for (int u = 0; u < U; ++u) {
-            double ph = 2 * PI * u / U;
-            m.positions.push_back(f3((float)(rad * std::cos(ph)), (float)y, (float)(rad * std::sin(ph))));
-            // weights: blend between joint j0 and j0+1 around the joint boundary
-            uint16_t ji[4] = {0, 0, 0, 0};
-            float w[4] = {1, 0, 0, 0};
-            if (j0 < 0) { ji[0] = 0; }
-            else if (j0 >= J - 1) { ji[0] = (uint16_t)(J - 1); }
-            else {
-                double t = jf - (j0 + 0.5);
-                ji[0] = (uint16_t)j0; ji[1] = (uint16_t)(j0 + 1);
-                w[0] = (float)(1.0 - t); w[1] = (float)t;
-            }
-            for (int k = 0; k < 4; ++k) { m.joint_indices.push_back(ji[k]); m.joint_weights.push_back(w[k]); }
-        }
-    }
-    Submesh s;
-    for (int r = 0; r + 1 < R; ++r)
-        for (int u = 0; u < U; ++u) {
-            uint32_t a = r * U + u, b = r * U + (u + 1) % U, c = (r + 1) * U + (u + 1) % U, d = (r + 1) * U + u;
-            s.indices.push_back(a); s.indices.push_back(c); s.indices.push_back(b);
-            s.indices.push_back(a); s.indices.push_back(d); s.indices.push_back(c);
-        }
-    s.material = default_material();
-    s.material.baseColor = f3(0.7f, 0.72f, 0.75f);
-    m.submeshes.push_back(std::move(s));
-    compute_vertex_normals(m);
-    m.uvs.assign(m.positions.size(), rt_float2{0.0f, 0.0f});
-    m.joint_count = (uint32_t)J;
-    auto skin = std::make_shared<Skin>();
-    for (int j = 0; j < J; ++j) {
-        skin->parent.push_back(j - 1);
-        float t[3] = {0.0f, j == 0 ? 0.0f : (float)seg, 0.0f};
-        skin->rest_local.push_back(m4_translate(t));
-    }
-    // global bind = chain of rest locals; inverse bind = translate(-y)
-    for (int j = 0; j < J; ++j) {
-        float t[3] = {0.0f, -(float)(seg * j), 0.0f};
-        skin->inverse_bind.push_back(m4_translate(t));
-    }
-    m.skin = skin;
-    return m;
-}
-
-}  // namespace rt
+#include <new>
 
 using namespace rt;
 
-struct rt_scene {
-    std::vector<Model> models;
-    std::vector<Light> lights;
-    std::string err;
-    struct Texture {
-        std::vector<uint8_t> texels;   // RGBA8, row 0 = top
-        uint32_t w = 0, h = 0;
-        std::string path;              // file it was decoded from (dedup of MTL maps)
-    };
-    std::vector<Texture> textures;
-    // flattened description caches
-    std::vector<rt_mesh_desc> mesh_descs;
-    std::vector<std::vector<rt_submesh_desc>> sub_descs;
-    std::vector<rt_texture_desc> tex_descs;
-};
-
-// Texture binding of one submesh slot (SubMesh.swift:117-166): flag bit + texture, and the base
-// color map replaces baseColor by white (:120-124).
-static void bind_slot(Submesh& sm, int slot, uint32_t id) {
-    sm.tex[slot] = (int32_t)id;
-    sm.material.textureFlags |= 1u << slot;
-    if (slot == 0) sm.material.baseColor = f3(1.0f, 1.0f, 1.0f);
+static bool find_texture(const rt_scene* s, const std::string& key, uint32_t* id) {
+    for (size_t i = 0; i < s->textures.size(); ++i)
+        if (!s->textures[i].path.empty() && s->textures[i].path == key) return *id = (uint32_t)i, true;
+    return false;
 }
 
-static rt_status load_png_file(rt_scene* s, const std::string& path, uint32_t* id) {
-    for (size_t i = 0; i < s->textures.size(); ++i)
-        if (!s->textures[i].path.empty() && s->textures[i].path == path) {
-            *id = (uint32_t)i;
-            return RT_OK;
-        }
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) {
-        s->err = "cannot open " + path;
-        return RT_ERR_IO;
-    }
-    std::vector<uint8_t> data;
-    uint8_t buf[1 << 16];
-    size_t n;
-    while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + n);
-    std::fclose(f);
-    rt_scene::Texture t;
-    char eb[256] = {0};
-    rt_status st = rt_decode_png(data.data(), data.size(), nullptr, &t.w, &t.h, eb, sizeof eb);
-    if (!st) {
-        t.texels.resize((size_t)t.w * t.h * 4);
-        st = rt_decode_png(data.data(), data.size(), t.texels.data(), &t.w, &t.h, eb, sizeof eb);
-    }
-    if (st) {
-        s->err = path + ": " + eb;
-        return st;
-    }
-    t.path = path;
-    s->textures.push_back(std::move(t));
-    *id = (uint32_t)(s->textures.size() - 1);
-    return RT_OK;
-}
-
-// ---- USD assets: the USDZ branch of Model.init (Model.swift:87-184) -----------------------------
-namespace usdscene {
-
-using usd::Attr;
-using usd::Prim;
-using usd::Stage;
-using usd::Value;
-
-static rt_status texture_from_bytes(rt_scene* s, const std::string& key, const uint8_t* data, size_t n, uint32_t* id) {
-    for (size_t i = 0; i < s->textures.size(); ++i)
-        if (!s->textures[i].path.empty() && s->textures[i].path == key) {
-            *id = (uint32_t)i;
-            return RT_OK;
-        }
+static rt_status add_png(rt_scene* s, const std::string& key, const uint8_t* data, size_t n, uint32_t* id,
+                         std::string* decoder_text) {   // two passes: the size, then the texels
     rt_scene::Texture t;
     char eb[256] = {0};
     rt_status st = rt_decode_png(data, n, nullptr, &t.w, &t.h, eb, sizeof eb);
@@ -713,497 +24,29 @@ static rt_status texture_from_bytes(rt_scene* s, const std::string& key, const u
         t.texels.resize((size_t)t.w * t.h * 4);
         st = rt_decode_png(data, n, t.texels.data(), &t.w, &t.h, eb, sizeof eb);
     }
-    if (st) return st;
+    if (st) {
+        if (decoder_text) *decoder_text = eb;
+        return st;
+    }
     t.path = key;
     s->textures.push_back(std::move(t));
     *id = (uint32_t)(s->textures.size() - 1);
     return RT_OK;
 }
 
-// simd_inverse (Model.swift:361): general 4x4 inverse (cofactors in double, rounded once)
-static M4 m4_inverse(const M4& a) {
-    double m[16], inv[16];
-    for (int i = 0; i < 16; ++i) m[i] = a.m[i];
-    inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
-    inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
-    inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
-    inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
-    inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
-    inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
-    inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
-    inv[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
-    inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
-    inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
-    inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
-    inv[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
-    inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
-    inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
-    inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
-    inv[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
-    const double det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12];
-    M4 r = m4_identity();
-    if (det == 0.0) return r;
-    for (int i = 0; i < 16; ++i) r.m[i] = (float)(inv[i] / det);
-    return r;
+rt_status rt_scene::texture_from_bytes(const std::string& key, const uint8_t* data, size_t n, uint32_t* id) {
+    return find_texture(this, key, id) ? RT_OK : add_png(this, key, data, n, id, nullptr);
 }
 
-// a USD matrix4d (row-vector convention, translation in the last row) is the simd float4x4 whose
-// columns are its rows (ModelIO's conversion)
-static M4 m4_from_usd(const std::vector<double>& v, size_t off) {
-    M4 r;
-    for (int i = 0; i < 16; ++i) r.m[i] = (float)v[off + i];
-    return r;
+rt_status rt_scene::texture_from_file(const std::string& path, uint32_t* id) {
+    if (find_texture(this, path, id)) return RT_OK;   // an MTL names one map many times: read it once
+    std::vector<uint8_t> data;
+    std::string text;
+    if (!read_file(path, 0, data, err)) return RT_ERR_IO;
+    const rt_status st = add_png(this, path, data.data(), data.size(), id, &text);
+    if (st) err = path + ": " + text;
+    return st;
 }
-
-// ---- joint paths (Model.swift:427-494) ----
-static std::vector<std::string> split_path(const std::string& p) {
-    std::vector<std::string> parts;
-    size_t i = 0;
-    while (i <= p.size()) {
-        size_t j = p.find('/', i);
-        if (j == std::string::npos) j = p.size();
-        if (j > i) parts.push_back(p.substr(i, j - i));
-        i = j + 1;
-    }
-    return parts;
-}
-static std::string join_path(const std::vector<std::string>& parts, size_t from) {
-    std::string r;
-    for (size_t k = from; k < parts.size(); ++k) r += (k > from ? "/" : "") + parts[k];
-    return r;
-}
-static std::string normalize_joint_path(const std::string& p) { return join_path(split_path(p), 0); }
-static std::string parent_joint_path(const std::string& p) {   // parentJointPath(for:)
-    const std::string n = normalize_joint_path(p);
-    const size_t s = n.find_last_of('/');
-    if (s == std::string::npos || s == 0) return std::string();
-    return n.substr(0, s);
-}
-static std::map<std::string, int> path_index_map(const std::vector<std::string>& paths) {   // buildPathIndexMap
-    std::vector<std::string> norm;
-    for (const auto& p : paths) norm.push_back(normalize_joint_path(p));
-    std::map<std::string, int> map;
-    for (size_t i = 0; i < norm.size(); ++i)
-        if (!norm[i].empty()) map[norm[i]] = (int)i;
-    std::map<std::string, int> suffix_count;
-    for (const auto& p : norm) {
-        if (p.empty()) continue;
-        const auto parts = split_path(p);
-        for (size_t st = 1; st < parts.size(); ++st) suffix_count[join_path(parts, st)]++;
-    }
-    for (size_t i = 0; i < norm.size(); ++i) {
-        if (norm[i].empty()) continue;
-        const auto parts = split_path(norm[i]);
-        for (size_t st = 1; st < parts.size(); ++st) {
-            const std::string suf = join_path(parts, st);
-            if (suffix_count[suf] == 1 && !map.count(suf)) map[suf] = (int)i;
-        }
-    }
-    return map;
-}
-static std::map<std::string, int> tail_index_map(const std::vector<std::string>& paths) {   // buildTailIndexMap
-    std::vector<std::string> tails;
-    for (const auto& p : paths) {
-        const auto parts = split_path(p);
-        tails.push_back(parts.empty() ? normalize_joint_path(p) : parts.back());
-    }
-    std::map<std::string, int> counts, map;
-    for (const auto& t : tails)
-        if (!t.empty()) counts[t]++;
-    for (size_t i = 0; i < tails.size(); ++i)
-        if (!tails[i].empty() && counts[tails[i]] == 1) map[tails[i]] = (int)i;
-    return map;
-}
-static int map_joint(const std::string& p, const std::map<std::string, int>& by_path, const std::map<std::string, int>& by_tail) {
-    const std::string n = normalize_joint_path(p);
-    auto it = by_path.find(n);
-    if (it != by_path.end()) return it->second;
-    const auto parts = split_path(n);
-    const std::string tail = parts.empty() ? n : parts.back();
-    auto jt = by_tail.find(tail);
-    return jt != by_tail.end() ? jt->second : -1;
-}
-
-// matrix_float4x4(simd_quatf) and matrix4x4_trs (Model.swift:496-501): T * R(q) * S
-static M4 m4_quat(const float q[4]) {   // q = (x, y, z, w)
-    const float x = q[0], y = q[1], z = q[2], w = q[3];
-    M4 r = m4_identity();
-    r.m[0] = w * w + x * x - y * y - z * z;
-    r.m[1] = 2.0f * (x * y + z * w);
-    r.m[2] = 2.0f * (x * z - y * w);
-    r.m[4] = 2.0f * (x * y - z * w);
-    r.m[5] = w * w - x * x + y * y - z * z;
-    r.m[6] = 2.0f * (y * z + x * w);
-    r.m[8] = 2.0f * (z * x + y * w);
-    r.m[9] = 2.0f * (y * z - x * w);
-    r.m[10] = w * w - x * x - y * y + z * z;
-    return r;
-}
-static M4 m4_trs(const float* t, const float* q, const float* sc) {
-    M4 S = m4_identity();
-    S.m[0] = sc[0];
-    S.m[5] = sc[1];
-    S.m[10] = sc[2];
-    return m4_mul(m4_mul(m4_translate(t), m4_quat(q)), S);
-}
-
-// MDLAnimatedValue sampling: clamped outside the keys, linear between them (spherical for
-// rotations, along the shorter arc)
-static void sample_track(const UsdSkel::Track& tr, double t, bool quat, std::vector<float>& out) {
-    out.clear();
-    if (tr.t.empty()) return;
-    if (t <= tr.t.front() || tr.t.size() == 1) { out = tr.v.front(); return; }
-    if (t >= tr.t.back()) { out = tr.v.back(); return; }
-    size_t k = 0;
-    while (k + 1 < tr.t.size() && tr.t[k + 1] <= t) ++k;
-    const std::vector<float>& a = tr.v[k];
-    const std::vector<float>& b = tr.v[k + 1];
-    const float u = (float)((t - tr.t[k]) / (tr.t[k + 1] - tr.t[k]));
-    const size_t n = std::min(a.size(), b.size());
-    out.resize(n);
-    if (!quat) {
-        for (size_t i = 0; i < n; ++i) out[i] = a[i] + (b[i] - a[i]) * u;
-        return;
-    }
-    for (size_t j = 0; j + 3 < n; j += 4) {
-        float q1[4] = {b[j], b[j + 1], b[j + 2], b[j + 3]};
-        float d = a[j] * q1[0] + a[j + 1] * q1[1] + a[j + 2] * q1[2] + a[j + 3] * q1[3];
-        if (d < 0.0f) { for (float& c : q1) c = -c; d = -d; }
-        float wa, wb;
-        if (d > 0.9995f) {
-            wa = 1.0f - u;
-            wb = u;
-        } else {
-            const float th = std::acos(d), st = std::sin(th);
-            wa = std::sin((1.0f - u) * th) / st;
-            wb = std::sin(u * th) / st;
-        }
-        float r[4], l = 0.0f;
-        for (int c = 0; c < 4; ++c) { r[c] = a[j + c] * wa + q1[c] * wb; l += r[c] * r[c]; }
-        l = std::sqrt(l);
-        for (int c = 0; c < 4; ++c) out[j + c] = l > 0.0f ? r[c] / l : r[c];
-    }
-}
-
-// Model.update(deltaTime:) at clip time t, then SkinningPass.updateSkinningJointMatrices
-// (SkinningPass.swift:124-157) for one mesh: geomBind^-1 * (global * invBind) * geomBind
-static void joint_matrices(const Mesh& m, double time_seconds, std::vector<M4>& out) {
-    const UsdSkel& S = *m.usd_skel;
-    const size_t J = S.joint_paths.size();
-    std::vector<M4> local = S.rest;
-    local.resize(J, m4_identity());
-    if (S.has_anim) {
-        const double t = S.duration > 0.0 ? std::fmod(time_seconds, S.duration) : 0.0;
-        std::vector<float> T, R, Sc;
-        sample_track(S.tr, t, false, T);
-        sample_track(S.rot, t, true, R);
-        sample_track(S.sc, t, false, Sc);
-        const size_t n = std::min(std::min(T.size() / 3, R.size() / 4), std::min(Sc.size() / 3, S.anim_paths.size()));
-        const auto by_path = path_index_map(S.joint_paths);
-        const auto by_tail = tail_index_map(S.joint_paths);
-        for (size_t i = 0; i < n; ++i) {
-            const int ji = map_joint(S.anim_paths[i], by_path, by_tail);
-            if (ji < 0 || (size_t)ji >= J) continue;
-            float q[4] = {R[4 * i + 1], R[4 * i + 2], R[4 * i + 3], R[4 * i]};   // stage order (w, x, y, z)
-            const float ql = std::sqrt(q[3] * q[3] + q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-            if (ql > 0.0001f) for (float& c : q) c = c / ql;
-            else { q[0] = q[1] = q[2] = 0.0f; q[3] = 1.0f; }
-            local[ji] = m4_trs(&T[3 * i], q, &Sc[3 * i]);
-        }
-    }
-    std::vector<M4> global = local;   // Skeleton.computeGlobalTransforms
-    for (size_t i = 0; i < J; ++i) {
-        const int p = S.parent[i];
-        if (p >= 0 && (size_t)p < i) global[i] = m4_mul(global[p], local[i]);
-    }
-    std::vector<M4> skin(J);
-    for (size_t j = 0; j < J; ++j) skin[j] = m4_mul(global[j], j < S.inverse_bind.size() ? S.inverse_bind[j] : m4_identity());
-    const std::vector<int>& map = m.joint_to_skel;
-    const size_t count = map.empty() ? std::max<size_t>(1, J) : map.size();
-    out.assign(count, m4_identity());
-    if (skin.empty()) return;
-    for (size_t i = 0; i < count; ++i) {
-        const int k = map.empty() ? (int)i : map[i];
-        const M4 sm = k >= 0 && (size_t)k < J ? skin[k] : m4_identity();
-        out[i] = m4_mul(m.geom_bind_inv, m4_mul(sm, m.geom_bind));
-    }
-}
-
-static const Value* attr_value(const Prim& p, const std::string& name, const Attr** out = nullptr) {
-    const Attr* a = p.attr(name);
-    if (out) *out = a;
-    if (!a) return nullptr;
-    if (a->has_default) return &a->value;
-    if (!a->samples.empty()) return &a->samples.front();   // first time sample (rest pose)
-    return nullptr;
-}
-
-static bool read_skeleton(const Stage& st, const Prim& sk, const Prim* anim, UsdSkel& out) {
-    const Value* joints = attr_value(sk, "joints");
-    if (!joints || joints->kind != Value::kStr) return false;
-    out.joint_paths = joints->str;
-    const size_t J = out.joint_paths.size();
-    const auto by_path = path_index_map(out.joint_paths);
-    for (const auto& p : out.joint_paths) {
-        const std::string pp = parent_joint_path(p);
-        auto it = pp.empty() ? by_path.end() : by_path.find(pp);
-        out.parent.push_back(it == by_path.end() ? -1 : it->second);
-    }
-    const Value* bind = attr_value(sk, "bindTransforms");
-    if (bind && bind->kind == Value::kNum && bind->num.size() == 16 * J)
-        for (size_t j = 0; j < J; ++j) out.inverse_bind.push_back(m4_inverse(m4_from_usd(bind->num, 16 * j)));
-    else
-        out.inverse_bind.assign(J, m4_identity());
-    const Value* rest = attr_value(sk, "restTransforms");
-    if (rest && rest->kind == Value::kNum && rest->num.size() == 16 * J)
-        for (size_t j = 0; j < J; ++j) out.rest.push_back(m4_from_usd(rest->num, 16 * j));
-    else
-        out.rest.assign(J, m4_identity());
-    if (!anim) return true;
-    const Value* aj = attr_value(*anim, "joints");
-    if (!aj || aj->kind != Value::kStr) return true;
-    out.has_anim = true;
-    out.anim_paths = aj->str;
-    const double tcps = st.time_codes_per_second > 0.0 ? st.time_codes_per_second : 24.0;
-    double tmin = 0.0, tmax = 0.0;
-    bool any = false;
-    auto track = [&](const char* name, int comps, UsdSkel::Track& tr) {
-        tr.comps = comps;
-        const Attr* a = anim->attr(name);
-        if (!a) return;
-        auto push = [&](double t, const Value& v) {
-            if (v.kind != Value::kNum) return;
-            std::vector<float> f(v.num.begin(), v.num.end());
-            tr.t.push_back(t);
-            tr.v.push_back(std::move(f));
-        };
-        if (!a->samples.empty()) {
-            std::vector<size_t> order(a->times.size());
-            for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-            std::sort(order.begin(), order.end(), [a](size_t x, size_t y) { return a->times[x] < a->times[y]; });
-            for (size_t i : order) push(a->times[i] / tcps, a->samples[i]);
-        } else if (a->has_default) {
-            push(0.0, a->value);
-        }
-        if (!tr.t.empty()) {
-            tmin = any ? std::min(tmin, tr.t.front()) : tr.t.front();
-            tmax = any ? std::max(tmax, tr.t.back()) : tr.t.back();
-            any = true;
-        }
-    };
-    track("translations", 3, out.tr);
-    track("rotations", 4, out.rot);
-    track("scales", 3, out.sc);
-    out.duration = any ? tmax - tmin : 0.0;   // AnimationClip.init (Model.swift:401-403)
-    return true;
-}
-
-// primvar value at (point, face-vertex corner, face) per its interpolation; -1 = none
-struct Primvar {
-    const Value* v = nullptr;
-    std::vector<int> idx;     // <name>:indices
-    std::string interp;
-    int comps = 0;
-    bool ok() const { return v && v->kind == Value::kNum && comps > 0; }
-    int key(int point, int corner, int face) const {
-        int k = interp == "faceVarying" ? corner : interp == "uniform" ? face : interp == "constant" ? 0 : point;
-        if (!idx.empty()) k = k < (int)idx.size() ? idx[k] : -1;
-        return k >= 0 && (size_t)(k + 1) * comps <= v->num.size() ? k : -1;
-    }
-};
-static Primvar primvar(const Prim& p, const std::string& name, const char* default_interp) {
-    Primvar pv;
-    const Attr* a = nullptr;
-    pv.v = attr_value(p, name, &a);
-    if (!pv.v || pv.v->kind != Value::kNum) { pv.v = nullptr; return pv; }
-    pv.comps = pv.v->comps;
-    pv.interp = a && !a->interpolation.empty() ? a->interpolation : default_interp;
-    if (const Value* iv = attr_value(p, name + ":indices"))
-        for (double d : iv->num) pv.idx.push_back(d >= 0.0 && d < 2147483647.0 ? (int)d : -1);
-    return pv;
-}
-
-static int find_prim_up(const Stage& st, int id, const char* rel) {   // inherited relationship target
-    for (int k = id; k >= 0; k = st.prims[k].parent) {
-        const auto* r = st.prims[k].rel(rel);
-        if (r && !r->empty()) return st.find((*r)[0]);
-    }
-    return -1;
-}
-
-static bool load_tex(rt_scene* s, const std::string& file, const std::vector<usd::PackageFile>& files, const std::string& dir,
-                     uint32_t* id) {
-    std::string f = file;
-    while (f.size() > 2 && f[0] == '.' && f[1] == '/') f = f.substr(2);
-    for (const auto& pf : files)
-        if (pf.name == f) return texture_from_bytes(s, "usdz:" + dir + ":" + f, pf.data.data(), pf.data.size(), id) == RT_OK;
-    return load_png_file(s, file[0] == '/' ? file : dir + "/" + f, id) == RT_OK;
-}
-
-// Material(material:) (SubMesh.swift:291-324) + the texture slots (SubMesh.swift:117-166) from a
-// UsdPreviewSurface: diffuseColor -> baseColor / base color map, emissiveColor -> emission /
-// emission map, ior, opacity (clamped) / opacity map, specularColor -> specular, normal /
-// roughness / metallic / occlusion -> their maps
-static void usd_material(rt_scene* s, const Stage& st, int mat, const std::vector<usd::PackageFile>& files,
-                         const std::string& dir, Submesh& sm) {
-    sm.material = default_material();
-    if (mat < 0) return;
-    int shader = -1;
-    if (const Attr* out = st.prims[mat].attr("outputs:surface"))
-        if (!out->connections.empty()) shader = st.find(out->connections[0].substr(0, out->connections[0].find_last_of('.')));
-    if (shader < 0) {
-        for (int k : st.preorder(mat, false)) {
-            const Value* id = attr_value(st.prims[k], "info:id");
-            if (st.prims[k].type == "Shader" && id && !id->str.empty() && id->str[0] == "UsdPreviewSurface") {
-                shader = k;
-                break;
-            }
-        }
-    }
-    if (shader < 0) return;
-    const Prim& sh = st.prims[shader];
-    auto texture_of = [&](const char* input) -> std::string {   // connected UsdUVTexture's file
-        const Attr* a = sh.attr(input);
-        if (!a || a->connections.empty()) return std::string();
-        const int t = st.find(a->connections[0].substr(0, a->connections[0].find_last_of('.')));
-        if (t < 0) return std::string();
-        const Value* f = attr_value(st.prims[t], "inputs:file");
-        return f && f->kind == Value::kStr && !f->str.empty() ? f->str[0] : std::string("?");
-    };
-    auto vec3 = [&](const char* input, rt_float3& dst) {
-        const Value* v = attr_value(sh, input);
-        if (v && v->kind == Value::kNum && v->num.size() >= 3) dst = f3((float)v->num[0], (float)v->num[1], (float)v->num[2]);
-    };
-    vec3("inputs:diffuseColor", sm.material.baseColor);
-    vec3("inputs:emissiveColor", sm.material.emission);
-    vec3("inputs:specularColor", sm.material.specular);
-    if (const Value* v = attr_value(sh, "inputs:ior"))
-        if (v->kind == Value::kNum && !v->num.empty()) sm.material.refractionIndex = (float)v->num[0];
-    if (const Value* v = attr_value(sh, "inputs:opacity"))
-        if (v->kind == Value::kNum && !v->num.empty()) sm.material.opacity = std::min(std::max((float)v->num[0], 0.0f), 1.0f);
-    static const struct { const char* input; int slot; } kMaps[] = {
-        {"inputs:diffuseColor", 0}, {"inputs:normal", 1}, {"inputs:roughness", 2}, {"inputs:metallic", 3},
-        {"inputs:occlusion", 4}, {"inputs:emissiveColor", 5}, {"inputs:opacity", 6}};
-    for (const auto& m : kMaps) {
-        const std::string file = texture_of(m.input);
-        if (file.empty()) continue;
-        if (m.slot == 0) sm.material.baseColor = f3(1.0f, 1.0f, 1.0f);   // a texture-typed base color (SubMesh.swift:299-302)
-        uint32_t id;
-        if (file != "?" && load_tex(s, file, files, dir, &id)) bind_slot(sm, m.slot, id);
-    }
-}
-
-// One UsdGeomMesh -> Mesh: fan triangulation, one vertex per unique (point, normal, uv) corner,
-// one submesh per materialBind GeomSubset (+ the faces no subset claims)
-static bool build_mesh(rt_scene* s, const Stage& st, int id, const std::vector<usd::PackageFile>& files,
-                       const std::string& dir, Mesh& out, std::string& err) {
-    const Prim& p = st.prims[id];
-    const Value* pts = attr_value(p, "points");
-    const Value* fvc = attr_value(p, "faceVertexCounts");
-    const Value* fvi = attr_value(p, "faceVertexIndices");
-    if (!pts || !fvc || !fvi || pts->kind != Value::kNum || pts->comps != 3) { err = p.path + ": mesh without points / faces"; return false; }
-    const int np = (int)(pts->num.size() / 3);
-    size_t total = 0;
-    for (double c : fvc->num) {   // NaN-safe: every count an integer within the index array
-        if (!(c >= 0.0 && c <= (double)fvi->num.size()) || c != std::floor(c)) { total = SIZE_MAX; break; }
-        total += (size_t)c;
-    }
-    if (total != fvi->num.size()) { err = p.path + ": faceVertexCounts do not match faceVertexIndices"; return false; }
-    for (double v : fvi->num)
-        if (!(v >= 0 && v < np)) { err = p.path + ": face vertex index out of range"; return false; }
-    Primvar nrm = primvar(p, "primvars:normals", "vertex");
-    if (!nrm.ok() || nrm.comps < 3) nrm = primvar(p, "normals", "vertex");
-    if (nrm.comps < 3) nrm.v = nullptr;   // normals need three components
-    Primvar uv = primvar(p, "primvars:st", "vertex");
-    if (!uv.ok())
-        for (const auto& kv : p.attrs)
-            if (kv.first.rfind("primvars:", 0) == 0 && kv.second.type.rfind("texCoord2", 0) == 0 &&
-                kv.first.find(":indices") == std::string::npos) {
-                uv = primvar(p, kv.first, "vertex");
-                break;
-            }
-    if (uv.comps < 2) uv.v = nullptr;   // texture coordinates need two components
-    Primvar ji = primvar(p, "primvars:skel:jointIndices", "vertex");
-    Primvar jw = primvar(p, "primvars:skel:jointWeights", "vertex");
-    int es = 1;
-    if (const Attr* a = p.attr("primvars:skel:jointIndices")) es = std::max(1, a->element_size);
-    out.name = p.name;
-    out.transform = m4_identity();
-    const bool skinned = ji.ok() && jw.ok();
-    // faces -> submesh (GeomSubset "materialBind" family)
-    const int nf = (int)fvc->num.size();
-    std::vector<int> face_sub(nf, -1);
-    std::vector<int> sub_mat;
-    for (int c : p.children) {
-        const Prim& g = st.prims[c];
-        if (g.type != "GeomSubset") continue;
-        const Value* fam = attr_value(g, "familyName");
-        if (fam && (fam->str.empty() || fam->str[0] != "materialBind")) continue;
-        const Value* ix = attr_value(g, "indices");
-        if (!ix) continue;
-        const int sid = (int)sub_mat.size();
-        sub_mat.push_back(find_prim_up(st, c, "material:binding"));
-        for (double f : ix->num)
-            if (f >= 0 && f < nf && face_sub[(int)f] < 0) face_sub[(int)f] = sid;
-    }
-    const int rest_sub = (int)sub_mat.size();
-    sub_mat.push_back(find_prim_up(st, id, "material:binding"));
-    std::vector<Submesh> subs(sub_mat.size());
-    for (size_t k = 0; k < subs.size(); ++k) usd_material(s, st, sub_mat[k], files, dir, subs[k]);
-    std::map<std::tuple<int, int, int>, uint32_t> dedup;
-    std::vector<uint32_t> poly;
-    size_t corner = 0;
-    for (int f = 0; f < nf; ++f) {
-        const int cnt = (int)fvc->num[f];
-        poly.clear();
-        for (int c = 0; c < cnt; ++c, ++corner) {
-            const int pt = (int)fvi->num[corner];
-            const int nk = nrm.ok() ? nrm.key(pt, (int)corner, f) : -1, uk = uv.ok() ? uv.key(pt, (int)corner, f) : -1;
-            auto key = std::make_tuple(pt, nk, uk);
-            auto it = dedup.find(key);
-            if (it == dedup.end()) {
-                const uint32_t v = (uint32_t)out.positions.size();
-                dedup.emplace(key, v);
-                out.positions.push_back(f3((float)pts->num[3 * pt], (float)pts->num[3 * pt + 1], (float)pts->num[3 * pt + 2]));
-                out.normals.push_back(nk >= 0 ? f3((float)nrm.v->num[3 * nk], (float)nrm.v->num[3 * nk + 1], (float)nrm.v->num[3 * nk + 2])
-                                              : f3(0, 0, 0));
-                rt_float2 t{0.0f, 0.0f};
-                if (uk >= 0) { t.x = (float)uv.v->num[uv.comps * uk]; t.y = (float)uv.v->num[uv.comps * uk + 1]; out.has_uvs = true; }
-                out.uvs.push_back(t);
-                if (skinned) {   // first four influences; Model.vertexDescriptor defaults otherwise
-                    uint16_t jix[4] = {0, 0, 0, 0};
-                    float w[4] = {1.0f, 0.0f, 0.0f, 0.0f};
-                    const int src = ji.interp == "constant" ? 0 : pt;
-                    if ((size_t)(src + 1) * es <= ji.v->num.size() && (size_t)(src + 1) * es <= jw.v->num.size()) {
-                        w[0] = 0.0f;
-                        for (int k = 0; k < std::min(es, 4); ++k) {
-                            const double j = ji.v->num[(size_t)src * es + k];
-                            jix[k] = (uint16_t)(j >= 0.0 && j <= 65535.0 ? j : 0.0);
-                            w[k] = (float)jw.v->num[(size_t)src * es + k];
-                        }
-                    }
-                    for (int k = 0; k < 4; ++k) { out.joint_indices.push_back(jix[k]); out.joint_weights.push_back(w[k]); }
-                }
-            }
-            poly.push_back(dedup[key]);
-        }
-        Submesh& sm = subs[face_sub[f] >= 0 ? face_sub[f] : rest_sub];
-        for (size_t k = 2; k < poly.size(); ++k) {
-            sm.indices.push_back(poly[0]);
-            sm.indices.push_back(poly[k - 1]);
-            sm.indices.push_back(poly[k]);
-        }
-    }
-    for (auto& sm : subs)
-        if (!sm.indices.empty()) out.submeshes.push_back(std::move(sm));
-    if (out.submeshes.empty()) { err = p.path + ": mesh without faces"; return false; }
-    if (!nrm.ok()) {   // addNormals(withAttributeNamed:creaseThreshold:) (Model.swift:136-138)
-        compute_vertex_normals(out);
-    }
-    return true;
-}
-
-}  // namespace usdscene
 
 static Light area_light_default() {  // Scene.setupLight (Scene.swift:161-169)
     Light l;
@@ -1227,6 +70,29 @@ static Light spot_light_default() {  // Light.spotLight(...) (Scene.swift:88, :2
     return l;
 }
 
+// The message of a caught exception, stored without letting that assignment throw in turn.
+static rt_status fail(rt_scene* s, rt_status st, const char* prefix, const char* what) noexcept {
+    try {
+        s->err = prefix ? std::string(prefix) + ": " + what : std::string(what);
+    } catch (...) {
+        s->err.clear();
+    }
+    return st;
+}
+// Nothing throws across the C-ABI: every entry point that can allocate runs its body
+// in here.  With `usd_path` every exception is RT_ERR_IO "path: what()": the asset is untrusted, an
+// allocation it asks for and does not get is an I/O error of that file.
+template <class Body>
+static rt_status guarded(rt_scene* s, Body&& body, const char* usd_path = nullptr) noexcept {
+    try {
+        return body();
+    } catch (const std::bad_alloc& e) {
+        return usd_path ? fail(s, RT_ERR_IO, usd_path, e.what()) : fail(s, RT_ERR_OUT_OF_MEMORY, nullptr, "out of memory");
+    } catch (const std::exception& e) {
+        return fail(s, RT_ERR_IO, usd_path, e.what());
+    }
+}
+
 extern "C" {
 
 void rt_material_override_glass(rt_material_override* out) {
@@ -1242,171 +108,41 @@ rt_status rt_scene_new(rt_scene** out) {
     rt_scene* s = new (std::nothrow) rt_scene();
     if (!s) return RT_ERR_OUT_OF_MEMORY;
     // Scene.init: lights = [light1 (area), light3 (spot)]; light2 is built but unused (Scene.swift:82-91)
-    s->lights.push_back(area_light_default());
-    s->lights.push_back(spot_light_default());
-    *out = s;
-    return RT_OK;
+    const rt_status st = guarded(s, [&] {
+        s->lights.push_back(area_light_default());
+        s->lights.push_back(spot_light_default());
+        return RT_OK;
+    });
+    if (st) delete s;
+    else *out = s;
+    return st;
 }
 
 rt_status rt_scene_free(rt_scene* scene) { delete scene; return RT_OK; }
 const char* rt_scene_last_error(const rt_scene* scene) { return scene ? scene->err.c_str() : "null scene"; }
 
-static void finish_model(rt_scene* s, Model&& model, const rt_material_override* ov) {
-    M4 T = model_transform(model.position, model.rotation, model.scale);
-    for (auto& m : model.meshes) {
-        m.transform = T;
-        for (auto& sm : m.submeshes) apply_override(sm.material, ov);  // Model.swift:198-205
-    }
-    s->models.push_back(std::move(model));
-}
-
 rt_status rt_scene_add_obj(rt_scene* s, const char* obj_path, const float position[3],
                            const float rotation[3], float scale, const rt_material_override* ov) {
     if (!s || !obj_path || !position) return RT_ERR_INVALID_ARG;
-    Model model;
-    model.name = obj_path;
-    for (int k = 0; k < 3; ++k) { model.position[k] = position[k]; model.rotation[k] = rotation ? rotation[k] : 0.0f; }
-    model.scale = scale;
-    std::string err;
-    if (!load_obj(obj_path, model.meshes, err)) { s->err = err; return RT_ERR_IO; }
-    for (auto& m : model.meshes)   // MTL maps; one that fails to load stays unbound (SubMesh.swift:100-107)
-        for (auto& sm : m.submeshes)
-            for (int k = 0; k < RT_TEXTURE_SLOTS; ++k) {
-                uint32_t id;
-                if (!sm.tex_path[k].empty() && load_png_file(s, sm.tex_path[k], &id) == RT_OK) bind_slot(sm, k, id);
-            }
-    s->err.clear();
-    finish_model(s, std::move(model), ov);
-    return RT_OK;
+    return guarded(s, [&] { return add_obj_impl(s, obj_path, position, rotation, scale, ov); });
 }
 
-static rt_status add_usd_impl(rt_scene* s, const char* path, const float position[3], const float rotation[3], float scale,
-                              const rt_material_override* ov);
-
-// The asset is untrusted: an allocation failure anywhere in reading or mapping it is an I/O error
-// of this call, never an exception across the C-ABI.
 rt_status rt_scene_add_usd(rt_scene* s, const char* path, const float position[3], const float rotation[3], float scale,
                            const rt_material_override* ov) {
     if (!s || !path || !position) return RT_ERR_INVALID_ARG;
-    try {
-        return add_usd_impl(s, path, position, rotation, scale, ov);
-    } catch (const std::exception& e) {
-        s->err = std::string(path) + ": " + e.what();
-        return RT_ERR_IO;
-    }
-}
-
-static rt_status add_usd_impl(rt_scene* s, const char* path, const float position[3], const float rotation[3], float scale,
-                              const rt_material_override* ov) {
-    usd::Stage st;
-    std::vector<usd::PackageFile> files;
-    std::string err;
-    if (!usd::load_stage(path, st, files, err)) {
-        s->err = std::string(path) + ": " + err;
-        return RT_ERR_IO;
-    }
-    Model model;
-    model.name = path;
-    for (int k = 0; k < 3; ++k) { model.position[k] = position[k]; model.rotation[k] = rotation ? rotation[k] : 0.0f; }
-    model.scale = scale;
-    // traverseAndFind (Model.swift:99-121): every MDLSkeleton / MDLPackedJointAnimation met on the
-    // depth-first walk replaces the previous one, so the last of each wins
-    std::vector<int> meshes;
-    int skel = -1, anim = -1;
-    for (int k : st.preorder(0, true)) {
-        const usd::Prim& p = st.prims[k];
-        if (p.type == "Skeleton") skel = k;
-        if (p.type == "SkelAnimation") anim = k;
-        if (p.type == "Mesh") meshes.push_back(k);
-    }
-    if (anim < 0 && skel >= 0) anim = usdscene::find_prim_up(st, skel, "skel:animationSource");
-    std::shared_ptr<UsdSkel> sk;
-    if (skel >= 0) {
-        sk = std::make_shared<UsdSkel>();
-        if (!usdscene::read_skeleton(st, st.prims[skel], anim >= 0 ? &st.prims[anim] : nullptr, *sk)) sk.reset();
-    }
-    const std::string dir = dir_of(path);
-    for (int id : meshes) {
-        Mesh m;
-        if (!usdscene::build_mesh(s, st, id, files, dir, m, err)) {
-            s->err = std::string(path) + ": " + err;
-            return RT_ERR_IO;
-        }
-        const usd::Prim& p = st.prims[id];
-        // MeshSkinningInfo (Model.swift:143-160): the mesh's joint order (skel:joints, else the
-        // skeleton's) mapped to skeleton indices; geometryBindTransform and its inverse
-        if (sk && !m.joint_indices.empty()) {
-            const usd::Value* jv = usdscene::attr_value(p, "skel:joints");
-            const std::vector<std::string>& jp = jv && jv->kind == usd::Value::kStr && !jv->str.empty() ? jv->str : sk->joint_paths;
-            const auto by_path = usdscene::path_index_map(sk->joint_paths);
-            const auto by_tail = usdscene::tail_index_map(sk->joint_paths);
-            for (const auto& j : jp) m.joint_to_skel.push_back(usdscene::map_joint(j, by_path, by_tail));
-            const usd::Value* gb = usdscene::attr_value(p, "primvars:skel:geomBindTransform");
-            m.geom_bind = gb && gb->num.size() == 16 ? usdscene::m4_from_usd(gb->num, 0) : m4_identity();
-            m.geom_bind_inv = usdscene::m4_inverse(m.geom_bind);
-            m.usd_skel = sk;
-            m.joint_count = (uint32_t)std::max<size_t>(1, m.joint_to_skel.size());
-            for (size_t v = 0; v < m.joint_indices.size(); ++v)
-                if (m.joint_indices[v] >= m.joint_count) {
-                    s->err = std::string(path) + ": " + p.path + ": joint index beyond the mesh's joints";
-                    return RT_ERR_IO;
-                }
-        } else {
-            m.joint_indices.clear();
-            m.joint_weights.clear();
-        }
-        model.meshes.push_back(std::move(m));
-    }
-    if (model.meshes.empty()) {
-        s->err = std::string(path) + ": no meshes";
-        return RT_ERR_IO;
-    }
-    s->err.clear();
-    finish_model(s, std::move(model), ov);
-    return RT_OK;
+    return guarded(s, [&] { return add_usd_impl(s, path, position, rotation, scale, ov); }, path);
 }
 
 rt_status rt_scene_add_procedural(rt_scene* s, const char* kind, const char* mtl_path,
                                   const float position[3], const float rotation[3], float scale,
                                   const rt_material_override* ov) {
     if (!s || !kind || !position) return RT_ERR_INVALID_ARG;
-    Model model;
-    model.name = kind;
-    for (int k = 0; k < 3; ++k) { model.position[k] = position[k]; model.rotation[k] = rotation ? rotation[k] : 0.0f; }
-    model.scale = scale;
-    std::string k = kind;
-    if (k == "dragon" || k == "knot") {
-        const double half[3] = {0.45, 0.3166, 0.2};
-        // "knot": the thin-tube torus-knot variant kept as a traversal torture test (rays refracted
-        // inside a long thin glass tube visit ~1000 boxes each)
-        Mesh m = k == "dragon" ? make_dragon(half) : make_knot("knot", 10627, 41, 0.42, 0.12, half);
-        // dragon.mtl: Kd 1 0 0, Ks .2, Ke 0, Ni 1, d 1 (AssetResources/dragon.mtl)
-        m.submeshes[0].material.baseColor = f3(1.0f, 0.0f, 0.0f);
-        m.submeshes[0].material.specular = f3(0.2f, 0.2f, 0.2f);
-        model.meshes.push_back(std::move(m));
-    } else if (k == "bunny") {
-        const double half[3] = {0.40, 0.3166, 0.32};
-        model.meshes.push_back(make_blob("bunny", 463, 76, half));
-    } else if (k == "robot") {
-        // height 3.0 units at scale 1 -> at the AppScene robot slot use scale ~0.5.
-        model.meshes.push_back(make_robot(5, 24, 96));
-    } else {
-        s->err = "unknown procedural kind " + k;
-        return RT_ERR_INVALID_ARG;
-    }
-    if (mtl_path) {
-        std::map<std::string, MtlEntry> mtl;
-        if (!parse_mtl(mtl_path, mtl) || mtl.empty()) { s->err = std::string("cannot read ") + mtl_path; return RT_ERR_IO; }
-        model.meshes[0].submeshes[0].material = mtl.begin()->second.material;
-    }
-    finish_model(s, std::move(model), ov);
-    return RT_OK;
+    return guarded(s, [&] { return add_procedural_impl(s, kind, mtl_path, position, rotation, scale, ov); });
 }
 
 rt_status rt_scene_set_lights(rt_scene* s, const Light* lights, uint32_t count) {
     if (!s || (count && !lights)) return RT_ERR_INVALID_ARG;
-    s->lights.assign(lights, lights + count);
-    return RT_OK;
+    return guarded(s, [&] { s->lights.assign(lights, lights + count); return RT_OK; });
 }
 
 rt_status rt_scene_set_light_intensity(rt_scene* s, float intensity) {
@@ -1423,193 +159,185 @@ static bool file_exists(const std::string& p) {
 
 rt_status rt_scene_preset(const char* name_c, const char* asset_dir_c, rt_scene** out, int32_t* is_synthetic) {
     if (!name_c || !out) return RT_ERR_INVALID_ARG;
-    std::string name = name_c, dir = asset_dir_c ? asset_dir_c : ".";
-    bool force_synth = false;
-    const std::string suf = "_synthetic";
-    if (name.size() > suf.size() && name.compare(name.size() - suf.size(), suf.size(), suf) == 0) {
-        force_synth = true;
-        name = name.substr(0, name.size() - suf.size());
-    }
     rt_scene* s = nullptr;
     rt_status st = rt_scene_new(&s);
     if (st) return st;
     int synth = 0;
-    const float zero[3] = {0, 0, 0};
-    auto obj = [&](const char* n, float px, float py, float pz, float sc) -> rt_status {
-        float p[3] = {px, py, pz};
-        return rt_scene_add_obj(s, (dir + "/" + n + ".obj").c_str(), p, zero, sc, nullptr);
-    };
-    // AppScene.swift:14-28 — models after the (optional) hero object
-    auto base = [&]() -> rt_status {
-        rt_status r;
-        if ((r = obj("plane", 0, 0, 0, 10))) return r;
-        if ((r = obj("sphere", -1.9f, 0.0f, 0.3f, 1))) return r;
-        if ((r = obj("sphere", 2.9f, 0.0f, -0.5f, 2))) return r;
-        return obj("plane-back", 0, 0, -1.5f, 10);
-    };
-    auto hero = [&](const char* kind, const rt_material_override* ov) -> rt_status {
-        float pos[3] = {0.3f, 0.38f, 2.5f};
-        float rot[3] = {0.0f, 3.14159265358979323846f / 2.0f * 1.2f, 0.0f};
-        std::string real = dir + "/" + kind + ".obj";
-        if (!force_synth && file_exists(real)) return rt_scene_add_obj(s, real.c_str(), pos, rot, 1.2f, ov);
-        synth = 1;
-        std::string mtl = dir + "/" + kind + ".mtl";
-        return rt_scene_add_procedural(s, kind, file_exists(mtl) ? mtl.c_str() : nullptr, pos, rot, 1.2f, ov);
-    };
-    rt_material_override glass;
-    rt_material_override_glass(&glass);
-    if (name == "c1") {
-        st = base();
-    } else if (name == "c2") {
-        if (!(st = hero("bunny", nullptr))) st = base();
-    } else if (name == "c3" || name == "c3g") {
-        if (!(st = hero("dragon", &glass))) st = base();
-    } else if (name == "c3d") {
-        if (!(st = hero("dragon", nullptr))) st = base();
-    } else if (name == "c3k") {
-        float pos[3] = {0.3f, 0.38f, 2.5f};
-        float rot[3] = {0.0f, 3.14159265358979323846f / 2.0f * 1.2f, 0.0f};
-        synth = 1;
-        std::string mtl = dir + "/dragon.mtl";
-        if (!(st = rt_scene_add_procedural(s, "knot", file_exists(mtl) ? mtl.c_str() : nullptr, pos, rot, 1.2f, &glass)))
-            st = base();
-    } else if (name == "c3r") {
-        // Irregular-geometry cross-check of the headline (not a BASELINE config): the reference's own
-        // modelled / scanned meshes in the dragon's place at about its triangle count, glass like
-        // C3g: a 4 x 4 wall of coatballs (AssetResources/coatball, 46,816 triangles each, ~12 units
-        // across) and a row of 8 teapots (15,704 triangles each) in front of it: 874,688 triangles.
-        for (int j = 0; j < 4 && !st; ++j)
-            for (int i = 0; i < 4 && !st; ++i) {
-                float p[3] = {0.3f + (i - 1.5f) * 0.27f, 0.50f + (j - 1.5f) * 0.2f, 2.5f};
-                st = rt_scene_add_obj(s, (dir + "/coatball/coatball.obj").c_str(), p, zero, 0.016f, &glass);
-            }
-        for (int k = 0; k < 8 && !st; ++k) {
-            float p[3] = {0.3f + (k - 3.5f) * 0.17f, 0.0f, 2.75f};
-            st = rt_scene_add_obj(s, (dir + "/teapot.obj").c_str(), p, zero, 0.001f, &glass);
+    st = guarded(s, [&] {
+        std::string name = name_c, dir = asset_dir_c ? asset_dir_c : ".";
+        bool force_synth = false;
+        const std::string suf = "_synthetic";
+        if (name.size() > suf.size() && name.compare(name.size() - suf.size(), suf.size(), suf) == 0) {
+            force_synth = true;
+            name = name.substr(0, name.size() - suf.size());
         }
-        if (!st) st = base();
-    } else if (name == "c5" || name == "app") {
-        float rp[3] = {-0.5f, 0.0f, 1.0f};
-        const std::string robot = dir + "/robot.usdz";
-        if (!force_synth && file_exists(robot)) {   // AppScene.swift:15: robot, scale 0.01
-            st = rt_scene_add_usd(s, robot.c_str(), rp, zero, 0.01f, nullptr);
-        } else {
+        const float zero[3] = {0, 0, 0};
+        auto obj = [&](const char* n, float px, float py, float pz, float sc) -> rt_status {
+            float p[3] = {px, py, pz};
+            return rt_scene_add_obj(s, (dir + "/" + n + ".obj").c_str(), p, zero, sc, nullptr);
+        };
+        // AppScene.swift:14-28 — models after the (optional) hero object
+        auto base = [&]() -> rt_status {
+            rt_status r;
+            if ((r = obj("plane", 0, 0, 0, 10))) return r;
+            if ((r = obj("sphere", -1.9f, 0.0f, 0.3f, 1))) return r;
+            if ((r = obj("sphere", 2.9f, 0.0f, -0.5f, 2))) return r;
+            return obj("plane-back", 0, 0, -1.5f, 10);
+        };
+        auto hero = [&](const char* kind, const rt_material_override* ov) -> rt_status {
+            float pos[3] = {0.3f, 0.38f, 2.5f};
+            float rot[3] = {0.0f, 3.14159265358979323846f / 2.0f * 1.2f, 0.0f};
+            std::string real = dir + "/" + kind + ".obj";
+            if (!force_synth && file_exists(real)) return rt_scene_add_obj(s, real.c_str(), pos, rot, 1.2f, ov);
             synth = 1;
-            st = rt_scene_add_procedural(s, "robot", nullptr, rp, zero, 0.5f, nullptr);
-        }
-        if (!st && name == "app") {
-            if (!(st = hero("dragon", &glass))) {
-                if (!(st = obj("train", -0.3f, 0.0f, 0.4f, 0.5f))) st = obj("treefir", 0.5f, 0.0f, -0.2f, 0.7f);
+            std::string mtl = dir + "/" + kind + ".mtl";
+            return rt_scene_add_procedural(s, kind, file_exists(mtl) ? mtl.c_str() : nullptr, pos, rot, 1.2f, ov);
+        };
+        rt_material_override glass;
+        rt_material_override_glass(&glass);
+        if (name == "c1") {
+            st = base();
+        } else if (name == "c2") {
+            if (!(st = hero("bunny", nullptr))) st = base();
+        } else if (name == "c3" || name == "c3g") {
+            if (!(st = hero("dragon", &glass))) st = base();
+        } else if (name == "c3d") {
+            if (!(st = hero("dragon", nullptr))) st = base();
+        } else if (name == "c3k") {
+            float pos[3] = {0.3f, 0.38f, 2.5f};
+            float rot[3] = {0.0f, 3.14159265358979323846f / 2.0f * 1.2f, 0.0f};
+            synth = 1;
+            std::string mtl = dir + "/dragon.mtl";
+            if (!(st = rt_scene_add_procedural(s, "knot", file_exists(mtl) ? mtl.c_str() : nullptr, pos, rot, 1.2f, &glass)))
+                st = base();
+        } else if (name == "c3r") {
+            // Irregular-geometry cross-check of the headline (not a BASELINE config): the reference's own
+            // modelled / scanned meshes in the dragon's place at about its triangle count, glass like
+            // C3g: a 4 x 4 wall of coatballs (AssetResources/coatball, 46,816 triangles each, ~12 units
+            // across) and a row of 8 teapots (15,704 triangles each) in front of it: 874,688 triangles.
+            for (int j = 0; j < 4 && !st; ++j)
+                for (int i = 0; i < 4 && !st; ++i) {
+                    float p[3] = {0.3f + (i - 1.5f) * 0.27f, 0.50f + (j - 1.5f) * 0.2f, 2.5f};
+                    st = rt_scene_add_obj(s, (dir + "/coatball/coatball.obj").c_str(), p, zero, 0.016f, &glass);
+                }
+            for (int k = 0; k < 8 && !st; ++k) {
+                float p[3] = {0.3f + (k - 3.5f) * 0.17f, 0.0f, 2.75f};
+                st = rt_scene_add_obj(s, (dir + "/teapot.obj").c_str(), p, zero, 0.001f, &glass);
             }
+            if (!st) st = base();
+        } else if (name == "c5" || name == "app") {
+            float rp[3] = {-0.5f, 0.0f, 1.0f};
+            const std::string robot = dir + "/robot.usdz";
+            if (!force_synth && file_exists(robot)) {   // AppScene.swift:15: robot, scale 0.01
+                st = rt_scene_add_usd(s, robot.c_str(), rp, zero, 0.01f, nullptr);
+            } else {
+                synth = 1;
+                st = rt_scene_add_procedural(s, "robot", nullptr, rp, zero, 0.5f, nullptr);
+            }
+            if (!st && name == "app") {
+                if (!(st = hero("dragon", &glass))) {
+                    if (!(st = obj("train", -0.3f, 0.0f, 0.4f, 0.5f))) st = obj("treefir", 0.5f, 0.0f, -0.2f, 0.7f);
+                }
+            }
+            if (!st) st = base();
+        } else {
+            s->err = "unknown preset " + name;
+            st = RT_ERR_INVALID_ARG;
         }
-        if (!st) st = base();
-    } else {
-        s->err = "unknown preset " + name;
-        st = RT_ERR_INVALID_ARG;
-    }
-    if (st) {
-        if (out) *out = s;  // let the caller read the error, then free
         return st;
-    }
-    if (is_synthetic) *is_synthetic = synth;
-    *out = s;
-    return RT_OK;
+    });
+    if (!st && is_synthetic) *is_synthetic = synth;
+    *out = s;  // on failure too: the caller reads the error, then frees
+    return st;
 }
 
 rt_status rt_scene_get_desc(rt_scene* s, rt_scene_desc* out) {
     if (!s || !out) return RT_ERR_INVALID_ARG;
-    s->mesh_descs.clear();
-    s->sub_descs.clear();
-    for (auto& model : s->models)
-        for (auto& m : model.meshes) {
-            std::vector<rt_submesh_desc> subs;
-            for (auto& sm : m.submeshes) {
-                rt_submesh_desc d;
+    return guarded(s, [&] {
+        s->mesh_descs.clear();
+        s->sub_descs.clear();
+        for (auto& model : s->models)
+            for (auto& m : model.meshes) {
+                std::vector<rt_submesh_desc> subs;
+                for (auto& sm : m.submeshes) {
+                    rt_submesh_desc d;
+                    std::memset(&d, 0, sizeof d);
+                    d.indices = sm.indices.data();
+                    d.index_count = (uint32_t)sm.indices.size();
+                    d.material = sm.material;
+                    for (int k = 0; k < 8; ++k) d.textures[k] = sm.tex[k];
+                    subs.push_back(d);
+                }
+                s->sub_descs.push_back(std::move(subs));   // the inner buffer stays put when the outer grows
+                rt_mesh_desc d;
                 std::memset(&d, 0, sizeof d);
-                d.indices = sm.indices.data();
-                d.index_count = (uint32_t)sm.indices.size();
-                d.material = sm.material;
-                for (int k = 0; k < 8; ++k) d.textures[k] = sm.tex[k];
-                subs.push_back(d);
+                d.positions = m.positions.data();
+                d.normals = m.normals.data();
+                d.uvs = m.has_uvs ? m.uvs.data() : nullptr;
+                d.joint_indices = m.joint_indices.empty() ? nullptr : m.joint_indices.data();
+                d.joint_weights = m.joint_weights.empty() ? nullptr : m.joint_weights.data();
+                d.vertex_count = (uint32_t)m.positions.size();
+                d.submesh_count = (uint32_t)m.submeshes.size();
+                d.submeshes = s->sub_descs.back().data();
+                d.transform = pack4x3(m.transform);
+                d.joint_count = m.joint_count;
+                s->mesh_descs.push_back(d);
             }
-            s->sub_descs.push_back(std::move(subs));
+        out->mesh_count = (uint32_t)s->mesh_descs.size();
+        out->meshes = s->mesh_descs.data();
+        out->light_count = (uint32_t)s->lights.size();
+        out->lights = s->lights.data();
+        s->tex_descs.clear();
+        for (auto& t : s->textures) {
+            rt_texture_desc d;
+            d.rgba8 = t.texels.data();
+            d.width = t.w;
+            d.height = t.h;
+            s->tex_descs.push_back(d);
         }
-    size_t k = 0;
-    for (auto& model : s->models)
-        for (auto& m : model.meshes) {
-            rt_mesh_desc d;
-            std::memset(&d, 0, sizeof d);
-            d.positions = m.positions.data();
-            d.normals = m.normals.data();
-            d.uvs = m.has_uvs ? m.uvs.data() : nullptr;
-            d.joint_indices = m.joint_indices.empty() ? nullptr : m.joint_indices.data();
-            d.joint_weights = m.joint_weights.empty() ? nullptr : m.joint_weights.data();
-            d.vertex_count = (uint32_t)m.positions.size();
-            d.submesh_count = (uint32_t)m.submeshes.size();
-            d.submeshes = s->sub_descs[k].data();
-            d.transform = pack4x3(m.transform);
-            d.joint_count = m.joint_count;
-            s->mesh_descs.push_back(d);
-            ++k;
-        }
-    out->mesh_count = (uint32_t)s->mesh_descs.size();
-    out->meshes = s->mesh_descs.data();
-    out->light_count = (uint32_t)s->lights.size();
-    out->lights = s->lights.data();
-    s->tex_descs.clear();
-    for (auto& t : s->textures) {
-        rt_texture_desc d;
-        d.rgba8 = t.texels.data();
-        d.width = t.w;
-        d.height = t.h;
-        s->tex_descs.push_back(d);
-    }
-    out->texture_count = (uint32_t)s->tex_descs.size();
-    out->_pad = 0;
-    out->textures = s->tex_descs.data();
-    return RT_OK;
+        out->texture_count = (uint32_t)s->tex_descs.size();
+        out->_pad = 0;
+        out->textures = s->tex_descs.data();
+        return RT_OK;
+    });
 }
 
 rt_status rt_scene_add_texture(rt_scene* s, const uint8_t* rgba8, uint32_t width, uint32_t height, uint32_t* id) {
     if (!s || !rgba8 || !id) return RT_ERR_INVALID_ARG;
-    if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28)) {
-        s->err = "bad texture size";
-        return RT_ERR_INVALID_ARG;
-    }
-    rt_scene::Texture t;
-    t.w = width;
-    t.h = height;
-    t.texels.assign(rgba8, rgba8 + (size_t)width * height * 4);
-    s->textures.push_back(std::move(t));
-    *id = (uint32_t)(s->textures.size() - 1);
-    return RT_OK;
+    return guarded(s, [&] {
+        if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28)) {
+            s->err = "bad texture size";
+            return RT_ERR_INVALID_ARG;
+        }
+        rt_scene::Texture t;
+        t.w = width;
+        t.h = height;
+        t.texels.assign(rgba8, rgba8 + (size_t)width * height * 4);
+        s->textures.push_back(std::move(t));
+        *id = (uint32_t)(s->textures.size() - 1);
+        return RT_OK;
+    });
 }
 
 rt_status rt_scene_load_texture(rt_scene* s, const char* png_path, uint32_t* id) {
     if (!s || !png_path || !id) return RT_ERR_INVALID_ARG;
-    return load_png_file(s, png_path, id);
+    return guarded(s, [&] { return s->texture_from_file(png_path, id); });
 }
 
 rt_status rt_scene_bind_texture(rt_scene* s, uint32_t mesh_index, uint32_t submesh_index, uint32_t slot,
                                 uint32_t texture_id) {
     if (!s) return RT_ERR_INVALID_ARG;
-    if (slot >= RT_TEXTURE_SLOTS || texture_id >= s->textures.size()) {
-        s->err = "bad texture slot / id";
-        return RT_ERR_INVALID_ARG;
-    }
-    uint32_t k = 0;
-    for (auto& model : s->models)
-        for (auto& m : model.meshes) {
-            if (k++ != mesh_index) continue;
-            if (submesh_index >= m.submeshes.size()) {
-                s->err = "bad submesh index";
-                return RT_ERR_INVALID_ARG;
-            }
-            bind_slot(m.submeshes[submesh_index], (int)slot, texture_id);
+    return guarded(s, [&] {
+        Mesh* m = mesh_at(s, mesh_index);
+        if (slot >= RT_TEXTURE_SLOTS || texture_id >= s->textures.size()) s->err = "bad texture slot / id";
+        else if (!m) s->err = "bad mesh index";
+        else if (submesh_index >= m->submeshes.size()) s->err = "bad submesh index";
+        else {
+            bind_slot(m->submeshes[submesh_index], (int)slot, texture_id);
             return RT_OK;
         }
-    s->err = "bad mesh index";
-    return RT_ERR_INVALID_ARG;
+        return RT_ERR_INVALID_ARG;
+    });
 }
 
 uint64_t rt_scene_triangle_count(const rt_scene* s) {
@@ -1624,37 +352,17 @@ uint64_t rt_scene_triangle_count(const rt_scene* s) {
 rt_status rt_scene_joint_matrices(rt_scene* s, uint32_t mesh_index, double time_seconds,
                                   float* out, uint32_t capacity, uint32_t* joint_count) {
     if (!s || !out) return RT_ERR_INVALID_ARG;
-    uint32_t k = 0;
-    Mesh* mesh = nullptr;
-    for (auto& model : s->models)
-        for (auto& m : model.meshes) { if (k == mesh_index) mesh = &m; ++k; }
-    if (!mesh || (!mesh->skin && !mesh->usd_skel)) { s->err = "mesh is not skinned"; return RT_ERR_INVALID_ARG; }
-    if (mesh->usd_skel) {
+    return guarded(s, [&] {
+        const Mesh* mesh = mesh_at(s, mesh_index);
+        if (!mesh || (!mesh->skin && !mesh->usd_skel)) { s->err = "mesh is not skinned"; return RT_ERR_INVALID_ARG; }
         std::vector<M4> jm;
-        usdscene::joint_matrices(*mesh, time_seconds, jm);
+        if (mesh->usd_skel) usd_joint_matrices(*mesh, time_seconds, jm);
+        else skin_joint_matrices(*mesh->skin, time_seconds, jm);
         if (capacity < jm.size()) return RT_ERR_INVALID_ARG;
         for (size_t j = 0; j < jm.size(); ++j) std::memcpy(out + 16 * j, jm[j].m, sizeof jm[j].m);
         if (joint_count) *joint_count = (uint32_t)jm.size();
         return RT_OK;
-    }
-    Skin& sk = *mesh->skin;
-    uint32_t J = (uint32_t)sk.parent.size();
-    if (capacity < J) return RT_ERR_INVALID_ARG;
-    // Model.update: local = rest * animated rotation; global via parents; joint = global * invBind
-    double t = std::fmod(time_seconds, sk.duration);
-    std::vector<M4> global(J);
-    for (uint32_t j = 0; j < J; ++j) {
-        float ang = (float)(0.35 * std::sin(6.283185307179586 * t / sk.duration + 0.9 * j) * (j == 0 ? 0.3 : 1.0));
-        M4 local = m4_mul(sk.rest_local[j], m4_rotate_axis(ang, 0, 0, 1));
-        global[j] = sk.parent[j] >= 0 ? m4_mul(global[sk.parent[j]], local) : local;
-    }
-    // SkinningPass.updateSkinningJointMatrices: geomBind^-1 * (global*invBind) * geomBind, geomBind = I
-    for (uint32_t j = 0; j < J; ++j) {
-        M4 jm = m4_mul(global[j], sk.inverse_bind[j]);
-        std::memcpy(out + 16 * j, jm.m, sizeof jm.m);
-    }
-    if (joint_count) *joint_count = J;
-    return RT_OK;
+    });
 }
 
 void rt_camera_orbit(int32_t width, int32_t height, const float target[3], float azimuth,

@@ -1,582 +1,14 @@
-// rt_usd.cpp — USD layer readers (.usda text, .usdc crate, .usdz package); see rt_usd.h.
-#include "rt_usd.h"
-#include <set>
-#include <sys/stat.h>
-
-#include <zlib.h>
+// rt_usd.cpp — the .usdc crate layer reader, with the LZ4 block decoder and the TfFastCompression
+// framing its sections use (see rt_usd.h).  The largest reader keeps the former single file's name and
+// history; beside it: rt_usda.cpp, rt_usdz.cpp, rt_usd_stage.cpp (shared), rt_usd_compose.cpp.
+#include "rt_usd_internal.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <functional>
-#include <memory>
 
 namespace rt {
 namespace usd {
-
-Stage::Stage() {
-    Prim root;
-    root.name = "";
-    root.path = "/";
-    prims.push_back(root);
-    by_path["/"] = 0;
-}
-
-int Stage::add_prim(int parent, const std::string& name) {
-    const std::string& pp = prims[parent].path;
-    std::string path = pp == "/" ? "/" + name : pp + "/" + name;
-    auto it = by_path.find(path);
-    if (it != by_path.end()) return it->second;
-    Prim p;
-    p.name = name;
-    p.path = path;
-    p.parent = parent;
-    prims.push_back(p);
-    const int id = (int)prims.size() - 1;
-    prims[parent].children.push_back(id);
-    by_path[path] = id;
-    return id;
-}
-
-int Stage::add_detached(const std::string& path) {
-    auto it = by_path.find(path);
-    if (it != by_path.end()) return it->second;
-    Prim p;
-    const size_t k = path.find_last_of('/');
-    p.name = k == std::string::npos ? path : path.substr(k + 1);
-    p.path = path;
-    prims.push_back(p);
-    const int id = (int)prims.size() - 1;
-    by_path[path] = id;
-    return id;
-}
-
-// primvar elementSize from a file number (1 when absent, NaN or out of range)
-static int element_size(double d) { return d >= 1.0 && d <= 65536.0 ? (int)d : 1; }
-
-std::vector<int> Stage::preorder(int root, bool active_only) const {
-    std::vector<int> out, todo{root};
-    std::vector<char> seen(prims.size(), 0);
-    while (!todo.empty()) {
-        const int k = todo.back();
-        todo.pop_back();
-        if (k < 0 || (size_t)k >= prims.size() || seen[k]) continue;
-        seen[k] = 1;
-        if (active_only && !prims[k].active) continue;
-        out.push_back(k);
-        const std::vector<int>& ch = prims[k].children;
-        for (size_t i = ch.size(); i-- > 0;) todo.push_back(ch[i]);
-    }
-    return out;
-}
-
-static float half_to_float(uint16_t h) {
-    const uint32_t s = (uint32_t)(h >> 15) << 31, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
-    uint32_t bits;
-    if (e == 0) {
-        if (m == 0) {
-            bits = s;
-        } else {   // subnormal: renormalise
-            int k = 0;
-            uint32_t mm = m;
-            while (!(mm & 0x400u)) { mm <<= 1; ++k; }
-            bits = s | ((uint32_t)(127 - 15 - k + 1) << 23) | ((mm & 0x3ffu) << 13);
-        }
-    } else if (e == 31) {
-        bits = s | 0x7f800000u | (m << 13);
-    } else {
-        bits = s | ((e - 15 + 127) << 23) | (m << 13);
-    }
-    float f;
-    std::memcpy(&f, &bits, 4);
-    return f;
-}
-
-// ---- .usda ------------------------------------------------------------------------------------
-namespace {
-
-struct Tok {
-    enum T { kEnd, kPunct, kIdent, kNum, kStr, kAsset, kPath, kErr } t = kEnd;
-    std::string s;
-    double v = 0.0;
-};
-
-class Lexer {
-public:
-    Lexer(const char* b, size_t n) : p_(b), e_(b + n) {}
-    const Tok& peek(size_t k = 0) {
-        while (buf_.size() <= k) buf_.push_back(lex());
-        return buf_[k];
-    }
-    Tok next() {
-        peek();
-        Tok t = std::move(buf_.front());
-        buf_.pop_front();
-        return t;
-    }
-    int line() const { return line_; }
-
-private:
-    const char* p_;
-    const char* e_;
-    int line_ = 1;
-    std::deque<Tok> buf_;
-
-    static bool ident_start(char c) { return std::isalpha((unsigned char)c) || c == '_'; }
-    static bool ident_char(char c) { return std::isalnum((unsigned char)c) || c == '_'; }
-
-    Tok lex() {
-        Tok t;
-        while (p_ < e_) {
-            if (*p_ == '\n') { ++line_; ++p_; }
-            else if (std::isspace((unsigned char)*p_)) ++p_;
-            else if (*p_ == '#') { while (p_ < e_ && *p_ != '\n') ++p_; }
-            else break;
-        }
-        if (p_ >= e_) return t;
-        const char c = *p_;
-        if (std::strchr("()[]{}=,:;", c)) {
-            t.t = Tok::kPunct;
-            t.s = std::string(1, c);
-            ++p_;
-            return t;
-        }
-        if (c == '"' || c == '\'') {
-            const bool triple = e_ - p_ >= 3 && p_[1] == c && p_[2] == c;
-            p_ += triple ? 3 : 1;
-            t.t = Tok::kStr;
-            while (p_ < e_) {
-                if (triple ? (e_ - p_ >= 3 && p_[0] == c && p_[1] == c && p_[2] == c) : *p_ == c) {
-                    p_ += triple ? 3 : 1;
-                    return t;
-                }
-                if (*p_ == '\\' && p_ + 1 < e_) {
-                    const char x = p_[1];
-                    t.s += x == 'n' ? '\n' : x == 't' ? '\t' : x;
-                    p_ += 2;
-                    continue;
-                }
-                if (*p_ == '\n') ++line_;
-                t.s += *p_++;
-            }
-            t.t = Tok::kErr;
-            return t;
-        }
-        if (c == '@') {
-            const bool triple = e_ - p_ >= 3 && p_[1] == '@' && p_[2] == '@';
-            p_ += triple ? 3 : 1;
-            t.t = Tok::kAsset;
-            while (p_ < e_) {
-                if (triple ? (e_ - p_ >= 3 && p_[0] == '@' && p_[1] == '@' && p_[2] == '@') : *p_ == '@') {
-                    p_ += triple ? 3 : 1;
-                    return t;
-                }
-                t.s += *p_++;
-            }
-            t.t = Tok::kErr;
-            return t;
-        }
-        if (c == '<') {
-            ++p_;
-            t.t = Tok::kPath;
-            while (p_ < e_ && *p_ != '>') t.s += *p_++;
-            if (p_ >= e_) { t.t = Tok::kErr; return t; }
-            ++p_;
-            return t;
-        }
-        const bool sign = (c == '-' || c == '+') && p_ + 1 < e_;
-        const char c1 = sign ? p_[1] : c;
-        if (std::isdigit((unsigned char)c1) || (c1 == '.' && p_ + (sign ? 2 : 1) < e_ && std::isdigit((unsigned char)p_[sign ? 2 : 1]))) {
-            char* end = nullptr;
-            t.v = std::strtod(p_, &end);
-            if (!end || end == p_) { t.t = Tok::kErr; return t; }
-            t.t = Tok::kNum;
-            p_ = end;
-            return t;
-        }
-        if (sign && e_ - p_ >= 4 && !std::strncmp(p_ + 1, "inf", 3)) {
-            t.t = Tok::kNum;
-            t.v = c == '-' ? -INFINITY : INFINITY;
-            p_ += 4;
-            return t;
-        }
-        if (ident_start(c)) {
-            t.t = Tok::kIdent;
-            // names: a:b:c, optionally followed by .timeSamples / .connect (property suffixes)
-            while (p_ < e_ && (ident_char(*p_) || ((*p_ == ':' || *p_ == '.') && p_ + 1 < e_ && ident_start(p_[1]))))
-                t.s += *p_++;
-            return t;
-        }
-        t.t = Tok::kErr;
-        t.s = std::string(1, c);
-        return t;
-    }
-};
-
-class UsdaParser {
-public:
-    UsdaParser(const char* b, size_t n, Stage& st) : lx_(b, n), st_(st) {}
-    bool run(std::string& err) {
-        if (lx_.peek().t == Tok::kPunct && lx_.peek().s == "(") {
-            if (!layer_meta()) return fail(err);
-        }
-        while (lx_.peek().t != Tok::kEnd) {
-            if (!is_ident({"def", "over", "class"})) { msg_ = "expected a prim"; return fail(err); }
-            if (!prim(0)) return fail(err);
-        }
-        return true;
-    }
-
-private:
-    Lexer lx_;
-    Stage& st_;
-    std::string msg_;
-
-    bool fail(std::string& err) {
-        err = "usda line " + std::to_string(lx_.line()) + ": " + (msg_.empty() ? "syntax error" : msg_);
-        return false;
-    }
-    bool is_punct(const char* s, size_t k = 0) { const Tok& t = lx_.peek(k); return t.t == Tok::kPunct && t.s == s; }
-    bool is_ident(std::initializer_list<const char*> names, size_t k = 0) {
-        const Tok& t = lx_.peek(k);
-        if (t.t != Tok::kIdent) return false;
-        for (const char* n : names)
-            if (t.s == n) return true;
-        return false;
-    }
-    bool expect(const char* p) {
-        if (!is_punct(p)) { msg_ = std::string("expected '") + p + "'"; return false; }
-        lx_.next();
-        return true;
-    }
-    // skips a balanced (...), [...] or {...} group starting at the current token
-    bool skip_group() {
-        int depth = 0;
-        do {
-            Tok t = lx_.next();
-            if (t.t == Tok::kEnd || t.t == Tok::kErr) { msg_ = "unbalanced group"; return false; }
-            if (t.t == Tok::kPunct && (t.s == "(" || t.s == "[" || t.s == "{")) ++depth;
-            if (t.t == Tok::kPunct && (t.s == ")" || t.s == "]" || t.s == "}")) --depth;
-        } while (depth > 0);
-        return true;
-    }
-
-    // nesting of values and prims is bounded: hostile input must not exhaust the stack
-    static constexpr int kMaxDepth = 64;
-    int depth_ = 0;
-    struct Nest {
-        int& d;
-        explicit Nest(int& d_) : d(d_) { ++d; }
-        ~Nest() { --d; }
-    };
-
-    bool value(Value& v) {
-        Nest nest(depth_);
-        if (depth_ > kMaxDepth) { msg_ = "values nested too deeply"; return false; }
-        const Tok& t = lx_.peek();
-        if (t.t == Tok::kPunct && t.s == "[") {
-            lx_.next();
-            v.array = true;
-            bool first = true;
-            while (!is_punct("]")) {
-                Value el;
-                if (!value(el)) return false;
-                if (el.kind == Value::kNum) {
-                    if (first) v.comps = (int)el.num.size();
-                    v.kind = Value::kNum;
-                    v.num.insert(v.num.end(), el.num.begin(), el.num.end());
-                } else if (el.kind == Value::kStr || el.kind == Value::kPath) {
-                    v.kind = el.kind;
-                    v.str.insert(v.str.end(), el.str.begin(), el.str.end());
-                }
-                first = false;
-                if (is_punct(",")) lx_.next();
-                else if (!is_punct("]")) { msg_ = "expected ',' or ']'"; return false; }
-            }
-            lx_.next();
-            if (v.kind == Value::kNone) v.kind = Value::kNum;   // empty array
-            return true;
-        }
-        if (t.t == Tok::kPunct && t.s == "(") {
-            lx_.next();
-            while (!is_punct(")")) {
-                Value el;
-                if (!value(el)) return false;
-                if (el.kind == Value::kNum) {
-                    v.kind = Value::kNum;
-                    v.num.insert(v.num.end(), el.num.begin(), el.num.end());
-                } else if (el.kind != Value::kNone) {
-                    v.kind = el.kind;
-                    v.str.insert(v.str.end(), el.str.begin(), el.str.end());
-                }
-                if (is_punct(",")) lx_.next();
-                else if (!is_punct(")")) { msg_ = "expected ',' or ')'"; return false; }
-            }
-            lx_.next();
-            v.comps = v.kind == Value::kNum ? (int)v.num.size() : 1;
-            return true;
-        }
-        if (t.t == Tok::kPunct && t.s == "{") return skip_group();   // dictionaries
-        Tok x = lx_.next();
-        switch (x.t) {
-        case Tok::kNum: v.kind = Value::kNum; v.num.push_back(x.v); return true;
-        case Tok::kStr:
-        case Tok::kAsset: v.kind = Value::kStr; v.str.push_back(x.s); return true;
-        case Tok::kPath: v.kind = Value::kPath; v.str.push_back(x.s); return true;
-        case Tok::kIdent:
-            if (x.s == "true" || x.s == "false") { v.kind = Value::kNum; v.num.push_back(x.s == "true" ? 1.0 : 0.0); return true; }
-            if (x.s == "None") { v.kind = Value::kNone; return true; }
-            if (x.s == "inf" || x.s == "nan") { v.kind = Value::kNum; v.num.push_back(x.s == "inf" ? INFINITY : NAN); return true; }
-            v.kind = Value::kStr;
-            v.str.push_back(x.s);
-            return true;
-        default: msg_ = "bad value"; return false;
-        }
-    }
-
-    // a reference / payload / sublayer list: None, one item or [items]; an item is @asset@, </path>
-    // or @asset@</path>, optionally followed by a (layer offset / custom data) group
-    bool arc_list(std::vector<Arc>& out) {
-        if (is_ident({"None"})) { lx_.next(); return true; }
-        const bool list = is_punct("[");
-        if (list) lx_.next();
-        while (!(list && is_punct("]"))) {
-            Arc a;
-            if (lx_.peek().t == Tok::kAsset) a.asset = lx_.next().s;
-            if (lx_.peek().t == Tok::kPath) a.path = lx_.next().s;
-            else if (a.asset.empty()) { msg_ = "expected a reference"; return false; }
-            if (is_punct("(") && !skip_group()) return false;
-            out.push_back(a);
-            if (!list) return true;
-            if (is_punct(",")) lx_.next();
-            else if (!is_punct("]")) { msg_ = "expected ',' or ']'"; return false; }
-        }
-        lx_.next();
-        return true;
-    }
-    // variants = { string set = "variant" ... }
-    bool variant_selection(int id) {
-        if (!expect("{")) return false;
-        while (!is_punct("}")) {
-            if (is_punct(";")) { lx_.next(); continue; }
-            if (lx_.peek().t == Tok::kIdent && lx_.peek(1).t != Tok::kPunct) lx_.next();   // value type
-            const Tok set = lx_.next();
-            if (set.t != Tok::kIdent && set.t != Tok::kStr) { msg_ = "expected a variant set name"; return false; }
-            if (!expect("=")) return false;
-            const Tok var = lx_.next();
-            if (var.t != Tok::kStr) { msg_ = "expected a variant name"; return false; }
-            st_.prims[id].variant_sel[set.s] = var.s;
-        }
-        lx_.next();
-        return true;
-    }
-
-    // arcs_for: -2 plain metadata, -1 the layer's (subLayers), >= 0 a prim's (references, payload,
-    // variants)
-    bool meta_entries(const std::function<void(const std::string&, const Value&)>& on, int arcs_for = -2) {
-        if (!expect("(")) return false;
-        while (!is_punct(")")) {
-            const Tok& t = lx_.peek();
-            if (t.t == Tok::kStr) { lx_.next(); continue; }   // doc string
-            if (t.t == Tok::kPunct && t.s == ";") { lx_.next(); continue; }
-            if (t.t != Tok::kIdent) { msg_ = "bad metadata"; return false; }
-            std::string op;
-            if (is_ident({"prepend", "append", "add", "delete", "reorder"}) && lx_.peek(1).t == Tok::kIdent) op = lx_.next().s;
-            std::string key = lx_.next().s;
-            if (lx_.peek().t == Tok::kIdent && !is_punct("=")) key = lx_.next().s;   // typed dictionary entry
-            if (!expect("=")) return false;
-            if (arcs_for >= -1 && (key == "references" || key == "payload" || key == "subLayers" || key == "inherits" ||
-                                   key == "specializes")) {
-                std::vector<Arc> arcs;
-                if (!arc_list(arcs)) return false;
-                if (op == "delete" || op == "reorder") continue;
-                if (arcs_for == -1 && key == "subLayers")
-                    for (const Arc& a : arcs) st_.sublayers.push_back(a.asset);
-                if (arcs_for >= 0 && key == "references") {
-                    auto& r = st_.prims[arcs_for].references;
-                    r.insert(op == "prepend" ? r.begin() : r.end(), arcs.begin(), arcs.end());
-                }
-                if (arcs_for >= 0 && key == "payload") {
-                    auto& r = st_.prims[arcs_for].payloads;
-                    r.insert(op == "prepend" ? r.begin() : r.end(), arcs.begin(), arcs.end());
-                }
-                continue;   // inherits / specializes: class arcs, not followed
-            }
-            if (arcs_for >= 0 && key == "variants") {
-                if (!variant_selection(arcs_for)) return false;
-                continue;
-            }
-            Value v;
-            if (!value(v)) return false;
-            on(key, v);
-        }
-        lx_.next();
-        return true;
-    }
-
-    bool layer_meta() {
-        return meta_entries([this](const std::string& k, const Value& v) {
-            if (k == "upAxis" && v.kind == Value::kStr && !v.str.empty()) st_.up_axis = v.str[0];
-            if (k == "defaultPrim" && v.kind == Value::kStr && !v.str.empty()) st_.default_prim = v.str[0];
-            if ((k == "timeCodesPerSecond" || k == "framesPerSecond") && v.kind == Value::kNum && !v.num.empty()) {
-                if (k == "timeCodesPerSecond" || !tcps_set_) st_.time_codes_per_second = v.num[0];
-                if (k == "timeCodesPerSecond") tcps_set_ = true;
-            }
-        }, -1);
-    }
-    bool tcps_set_ = false;
-
-    bool prim(int parent) {
-        Nest nest(depth_);
-        if (depth_ > kMaxDepth) { msg_ = "prims nested too deeply"; return false; }
-        lx_.next();   // specifier
-        std::string type;
-        if (lx_.peek().t == Tok::kIdent) type = lx_.next().s;
-        if (lx_.peek().t != Tok::kStr) { msg_ = "expected a prim name"; return false; }
-        const std::string name = lx_.next().s;
-        const int id = st_.add_prim(parent, name);
-        if (!type.empty()) st_.prims[id].type = type;
-        if (is_punct("(") && !prim_meta(id)) return false;
-        return prim_body(id);
-    }
-    bool prim_meta(int id) {
-        return meta_entries([this, id](const std::string& k, const Value& v) {
-            Prim& p = st_.prims[id];
-            if (k == "apiSchemas")
-                for (const auto& s : v.str) p.api_schemas.push_back(s);
-            if (k == "active" && v.kind == Value::kNum && !v.num.empty()) p.active = v.num[0] != 0.0;
-        }, id);
-    }
-    // { properties, child prims, variant sets } of prim id (or of a variant body)
-    bool prim_body(int id) {
-        if (!expect("{")) return false;
-        while (!is_punct("}")) {
-            if (lx_.peek().t == Tok::kEnd) { msg_ = "unterminated prim"; return false; }
-            if (is_ident({"def", "over", "class"})) {
-                if (!prim(id)) return false;
-            } else if (is_ident({"variantSet"})) {
-                // variantSet "set" = { "variant" (metadata) { body } ... }: each body is kept as a
-                // detached prim "/Prim{set=variant}"; load_stage applies the selected one
-                Nest nest(depth_);
-                if (depth_ > kMaxDepth) { msg_ = "prims nested too deeply"; return false; }
-                lx_.next();
-                const Tok set = lx_.next();
-                if (set.t != Tok::kStr) { msg_ = "expected a variant set name"; return false; }
-                if (!expect("=") || !expect("{")) return false;
-                while (!is_punct("}")) {
-                    const Tok var = lx_.next();
-                    if (var.t != Tok::kStr) { msg_ = "expected a variant name"; return false; }
-                    const int body = st_.add_detached(st_.prims[id].path + "{" + set.s + "=" + var.s + "}");
-                    st_.prims[id].variant_bodies[set.s][var.s] = body;
-                    if (is_punct("(") && !prim_meta(body)) return false;
-                    if (!prim_body(body)) return false;
-                }
-                lx_.next();
-            } else if (is_ident({"reorder"})) {
-                lx_.next();
-                lx_.next();
-                if (!expect("=")) return false;
-                Value v;
-                if (!value(v)) return false;
-            } else if (is_punct(";")) {
-                lx_.next();
-            } else if (!property(id)) {
-                return false;
-            }
-        }
-        lx_.next();
-        return true;
-    }
-
-    bool property(int id) {
-        bool uniform = false;
-        while (is_ident({"custom", "uniform", "varying", "config", "prepend", "append", "add", "delete"})) {
-            if (lx_.peek().s == "uniform") uniform = true;
-            lx_.next();
-        }
-        if (lx_.peek().t != Tok::kIdent) { msg_ = "expected a property"; return false; }
-        if (lx_.peek().s == "rel") {
-            lx_.next();
-            if (lx_.peek().t != Tok::kIdent) { msg_ = "expected a relationship name"; return false; }
-            std::string name = lx_.next().s;
-            auto& targets = st_.prims[id].rels[name];
-            if (is_punct("=")) {
-                lx_.next();
-                Value v;
-                if (!value(v)) return false;
-                if (v.kind == Value::kPath) targets = v.str;
-            }
-            if (is_punct("(") && !meta_entries([](const std::string&, const Value&) {})) return false;
-            return true;
-        }
-        std::string type = lx_.next().s;
-        if (is_punct("[") && is_punct("]", 1)) {
-            lx_.next();
-            lx_.next();
-            type += "[]";
-        }
-        if (lx_.peek().t != Tok::kIdent) { msg_ = "expected an attribute name"; return false; }
-        std::string name = lx_.next().s;
-        bool ts = false, conn = false;
-        auto strip = [&name](const char* suf) {
-            const size_t n = std::strlen(suf);
-            if (name.size() > n && name.compare(name.size() - n, n, suf) == 0) { name.resize(name.size() - n); return true; }
-            return false;
-        };
-        if (strip(".timeSamples")) ts = true;
-        else if (strip(".connect")) conn = true;
-        else strip(".spline");
-        Attr& a = st_.prims[id].attrs[name];
-        a.type = type;
-        a.uniform = a.uniform || uniform;
-        if (is_punct("=")) {
-            lx_.next();
-            if (ts) {
-                if (!expect("{")) return false;
-                while (!is_punct("}")) {
-                    Tok k = lx_.next();
-                    if (k.t != Tok::kNum) { msg_ = "expected a time code"; return false; }
-                    if (!expect(":")) return false;
-                    Value v;
-                    if (!value(v)) return false;
-                    a.times.push_back(k.v);
-                    a.samples.push_back(v);
-                    if (is_punct(",")) lx_.next();
-                }
-                lx_.next();
-            } else if (conn) {
-                Value v;
-                if (!value(v)) return false;
-                if (v.kind == Value::kPath) a.connections = v.str;
-            } else {
-                Value v;
-                if (!value(v)) return false;
-                if (v.kind != Value::kNone) {
-                    a.value = v;
-                    a.has_default = true;
-                }
-            }
-        }
-        if (is_punct("(")) {
-            if (!meta_entries([&a](const std::string& k, const Value& v) {
-                    if (k == "interpolation" && v.kind == Value::kStr && !v.str.empty()) a.interpolation = v.str[0];
-                    if (k == "elementSize" && v.kind == Value::kNum && !v.num.empty()) a.element_size = element_size(v.num[0]);
-                }))
-                return false;
-        }
-        return true;
-    }
-};
-
-}  // namespace
-
-bool parse_usda(const char* text, size_t n, Stage& st, std::string& err) {
-    UsdaParser p(text, n, st);
-    return p.run(err);
-}
 
 // ---- LZ4 block + TfFastCompression framing ---------------------------------------------------
 bool lz4_block_decode(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_n) {
@@ -638,56 +70,6 @@ static bool fast_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t c
         total += got;
     }
     *out_n = total;
-    return true;
-}
-
-// ---- .usdz (zip) ------------------------------------------------------------------------------
-static uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-static uint32_t rd32(const uint8_t* p) { return rd16(p) | (rd16(p + 2) << 16); }
-
-bool read_zip(const uint8_t* data, size_t n, std::vector<PackageFile>& files, std::string& err) {
-    if (n < 22) { err = "zip: too short"; return false; }
-    size_t eocd = (size_t)-1;
-    for (size_t i = n - 22 + 1; i-- > 0 && n - i <= 22 + 65535;)
-        if (rd32(data + i) == 0x06054b50u) { eocd = i; break; }
-    if (eocd == (size_t)-1) { err = "zip: no end-of-central-directory record"; return false; }
-    const uint32_t entries = rd16(data + eocd + 10), cd_off = rd32(data + eocd + 16);
-    size_t p = cd_off;
-    for (uint32_t e = 0; e < entries; ++e) {
-        if (p + 46 > n || rd32(data + p) != 0x02014b50u) { err = "zip: bad central directory"; return false; }
-        const uint32_t method = rd16(data + p + 10), csize = rd32(data + p + 20), usize = rd32(data + p + 24);
-        const uint32_t nlen = rd16(data + p + 28), elen = rd16(data + p + 30), clen = rd16(data + p + 32);
-        const uint32_t lho = rd32(data + p + 42);
-        if (p + 46 + nlen > n) { err = "zip: bad entry name"; return false; }
-        PackageFile f;
-        f.name.assign((const char*)data + p + 46, nlen);
-        p += 46 + nlen + elen + clen;
-        if (csize == 0xffffffffu || usize == 0xffffffffu || lho == 0xffffffffu) { err = "zip: zip64 entries unsupported"; return false; }
-        if (!f.name.empty() && f.name.back() == '/') continue;
-        if ((size_t)lho + 30 > n || rd32(data + lho) != 0x04034b50u) { err = "zip: bad local header"; return false; }
-        const size_t off = (size_t)lho + 30 + rd16(data + lho + 26) + rd16(data + lho + 28);
-        if (off + csize > n) { err = "zip: truncated entry " + f.name; return false; }
-        if (method == 0) {
-            f.data.assign(data + off, data + off + csize);
-        } else if (method == 8) {
-            if ((uint64_t)usize > 1032ull * csize + 1024) { err = "zip: implausible size of " + f.name; return false; }
-            f.data.resize(usize);
-            z_stream zs;
-            std::memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, -MAX_WBITS) != Z_OK) { err = "zip: inflateInit2"; return false; }
-            zs.next_in = const_cast<Bytef*>(data + off);
-            zs.avail_in = csize;
-            zs.next_out = f.data.data();
-            zs.avail_out = usize;
-            const int r = inflate(&zs, Z_FINISH);
-            inflateEnd(&zs);
-            if (r != Z_STREAM_END || zs.total_out != usize) { err = "zip: inflate failed for " + f.name; return false; }
-        } else {
-            err = "zip: compression method " + std::to_string(method) + " unsupported (" + f.name + ")";
-            return false;
-        }
-        files.push_back(std::move(f));
-    }
     return true;
 }
 
@@ -1416,375 +798,6 @@ private:
 bool parse_usdc(const uint8_t* data, size_t n, Stage& st, std::string& err) {
     Crate c(data, n);
     return c.run(st, err);
-}
-
-static bool parse_layer(const uint8_t* data, size_t n, Stage& st, std::string& err) {
-    if (n >= 8 && !std::memcmp(data, "PXR-USDC", 8)) return parse_usdc(data, n, st, err);
-    if (n >= 5 && !std::memcmp(data, "#usda", 5)) return parse_usda((const char*)data, n, st, err);
-    err = "not a USD layer (neither PXR-USDC nor #usda)";
-    return false;
-}
-
-// ---- composition ------------------------------------------------------------------------------
-namespace {
-
-constexpr int kMaxArcDepth = 16;              // nested layer loads (sublayer / reference chains)
-constexpr size_t kMaxComposedPrims = 1u << 17;  // prims a composition may create (hostile fan-out)
-constexpr uint64_t kMaxLayerBytes = 1ull << 31;   // a referenced layer file (regular files only)
-constexpr uint64_t kMaxComposedBytes = 4ull << 30;   // attribute data merges may copy (hostile fan-out)
-
-std::string dir_of(const std::string& id) {
-    const size_t k = id.find_last_of('/');
-    return k == std::string::npos ? std::string() : id.substr(0, k + 1);
-}
-// collapses "." and ".." segments (a leading "/" is kept)
-std::string normalize(const std::string& p) {
-    std::vector<std::string> seg;
-    size_t b = 0;
-    while (b <= p.size()) {
-        size_t e = p.find('/', b);
-        if (e == std::string::npos) e = p.size();
-        const std::string x = p.substr(b, e - b);
-        if (x == "..") { if (!seg.empty() && seg.back() != "..") seg.pop_back(); else seg.push_back(x); }
-        else if (!x.empty() && x != ".") seg.push_back(x);
-        b = e + 1;
-    }
-    std::string out = !p.empty() && p[0] == '/' ? "/" : "";
-    for (size_t k = 0; k < seg.size(); ++k) out += (k ? "/" : "") + seg[k];
-    return out;
-}
-// a path of the source subtree rooted at `from`, moved under `to`
-std::string remap(const std::string& x, const std::string& from, const std::string& to) {
-    if (from.empty() || from == to || x.compare(0, from.size(), from) != 0) return x;
-    if (x.size() > from.size() && x[from.size()] != '/' && x[from.size()] != '.') return x;
-    return to + x.substr(from.size());
-}
-
-class Composer {
-public:
-    explicit Composer(const std::vector<PackageFile>* pkg) : pkg_(pkg) {}
-    std::string err;
-
-    // layer `id` parsed and composed; shared by every arc that names it (no copy per arc)
-    std::shared_ptr<const Stage> load(const std::string& id, int depth) {
-        if (depth > kMaxArcDepth) {
-            fail("composition nested deeper than " + std::to_string(kMaxArcDepth) + " layers");
-            return nullptr;
-        }
-        auto c = cache_.find(id);
-        if (c != cache_.end()) return c->second;
-        if (loading_.count(id)) {
-            fail("composition cycle through " + id);
-            return nullptr;
-        }
-        std::vector<uint8_t> data;
-        if (!read(id, data)) {
-            fail("cannot open layer " + id);
-            return nullptr;
-        }
-        auto L = std::make_shared<Stage>();
-        L->layer_id = id;
-        std::string e;
-        if (!parse_layer(data.data(), data.size(), *L, e)) {
-            fail(id + ": " + e);
-            return nullptr;
-        }
-        loading_.insert(id);
-        const bool ok = compose(id, *L, depth);
-        loading_.erase(id);
-        if (!ok) return nullptr;
-        cache_[id] = L;
-        return L;
-    }
-
-    // sublayers under the layer's own opinions, then every prim's arcs in namespace order.  Variant
-    // selections are composed in the root layer (depth 0) only: a sublayer or referenced layer keeps
-    // its selections and variant bodies unapplied, so the strongest selection of the whole stack
-    // (the root's own, then its sublayers', then the referenced layers') picks the variant.
-    bool compose(const std::string& id, Stage& L, int depth) {
-        L.layer_id = id;
-        const std::vector<std::string> subs = L.sublayers;
-        L.sublayers.clear();
-        for (const std::string& sub : subs) {
-            const std::shared_ptr<const Stage> S = load(resolve(id, sub), depth + 1);
-            if (!S) return false;
-            if (!merge(L, 0, *S, 0, "", "")) return false;
-            if (L.default_prim.empty()) L.default_prim = S->default_prim;
-        }
-        std::vector<int> todo{0};
-        std::vector<uint8_t> seen;   // each prim once, whatever its children lists say
-        while (!todo.empty()) {
-            const int p = todo.back();
-            todo.pop_back();
-            if ((size_t)p >= seen.size()) seen.resize(L.prims.size() + 1, 0);
-            if (seen[p]) continue;
-            seen[p] = 1;
-            if (!apply_arcs(id, L, p, depth, depth == 0)) return false;
-            const std::vector<int>& ch = L.prims[p].children;
-            for (auto it = ch.rbegin(); it != ch.rend(); ++it) todo.push_back(*it);
-        }
-        return true;
-    }
-
-private:
-    const std::vector<PackageFile>* pkg_;
-    std::set<std::string> loading_;
-    std::map<std::string, std::shared_ptr<const Stage>> cache_;
-    size_t budget_ = kMaxComposedPrims;
-    uint64_t bytes_budget_ = kMaxComposedBytes;
-
-    bool fail(const std::string& m) {
-        err = m;
-        return false;
-    }
-    // composition work (prims merged, arcs applied, internal snapshots copied) is bounded: a
-    // hostile list of a million arcs must fail fast, not merge a subtree a million times
-    bool spend(size_t n) {
-        if (n > budget_) return fail("composed stage larger than " + std::to_string(kMaxComposedPrims) + " prims");
-        budget_ -= n;
-        return true;
-    }
-    // and so are the attribute bytes merges copy: a few references to one large mesh layer must
-    // not multiply its arrays into terabytes
-    bool spend_bytes(uint64_t n) {
-        if (n > bytes_budget_) return fail("composed attribute data larger than " + std::to_string(kMaxComposedBytes >> 20) + " MiB");
-        bytes_budget_ -= n;
-        return true;
-    }
-    static uint64_t value_bytes(const Value& v) {
-        uint64_t b = 8 * (uint64_t)v.num.size() + 32;
-        for (const std::string& s : v.str) b += s.size() + 32;
-        return b;
-    }
-    static uint64_t attr_bytes(const Attr& a) {
-        uint64_t b = value_bytes(a.value) + 8 * (uint64_t)a.times.size();
-        for (const Value& v : a.samples) b += value_bytes(v);
-        for (const std::string& s : a.connections) b += s.size() + 32;
-        return b;
-    }
-    // what a copy of a whole stage copies (an internal arc's snapshot of its layer)
-    static uint64_t stage_bytes(const Stage& L) {
-        uint64_t b = 0;
-        for (const Prim& pr : L.prims) {
-            b += 256;
-            for (const auto& kv : pr.attrs) b += attr_bytes(kv.second);
-        }
-        return b;
-    }
-    // an asset path relative to the layer naming it (inside the package for a .usdz)
-    std::string resolve(const std::string& from, const std::string& asset) const {
-        if (!asset.empty() && asset[0] == '/') return normalize(pkg_ ? asset.substr(1) : asset);
-        return normalize(dir_of(from) + asset);
-    }
-    bool read(const std::string& id, std::vector<uint8_t>& data) const {
-        if (pkg_) {
-            for (const PackageFile& f : *pkg_)
-                if (normalize(f.name) == id) { data = f.data; return true; }
-            return false;
-        }
-        // an asset path comes from the file: only a regular file of bounded size is read (a
-        // reference to /dev/zero or a FIFO must not hang the loader)
-        struct stat sb;
-        if (stat(id.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode) || (uint64_t)sb.st_size > kMaxLayerBytes) return false;
-        FILE* f = std::fopen(id.c_str(), "rb");
-        if (!f) return false;
-        uint8_t buf[1 << 16];
-        size_t k;
-        while ((k = std::fread(buf, 1, sizeof buf, f)) > 0 && data.size() <= kMaxLayerBytes) data.insert(data.end(), buf, buf + k);
-        std::fclose(f);
-        return data.size() <= kMaxLayerBytes;
-    }
-
-    // Prim s of S (and its subtree) merged into prim d of D as the weaker opinion: only what D does
-    // not author is taken; paths under `from` move under `to`.  S may be D (a variant body).
-    bool merge(Stage& D, int d, const Stage& S, int s, const std::string from, const std::string to) {   // paths by value: D.prims may move
-        std::vector<std::pair<int, int>> work{{d, s}};
-        while (!work.empty()) {
-            const auto [dd, ss] = work.back();
-            work.pop_back();
-            if (!spend(1)) return false;
-            const Prim src = S.prims[ss];   // a copy: D's prims may move below when S is D
-            Prim& dp = D.prims[dd];
-            if (dp.type.empty()) dp.type = src.type;
-            for (const std::string& a : src.api_schemas)
-                if (std::find(dp.api_schemas.begin(), dp.api_schemas.end(), a) == dp.api_schemas.end()) dp.api_schemas.push_back(a);
-            for (const auto& kv : src.attrs) {
-                if (dp.attrs.count(kv.first)) continue;
-                if (!spend_bytes(attr_bytes(kv.second))) return false;
-                Attr a = kv.second;
-                for (std::string& c : a.connections) c = remap(c, from, to);
-                dp.attrs.emplace(kv.first, std::move(a));
-            }
-            for (const auto& kv : src.rels) {
-                if (dp.rels.count(kv.first)) continue;
-                std::vector<std::string> t = kv.second;
-                for (std::string& x : t) x = remap(x, from, to);
-                dp.rels.emplace(kv.first, std::move(t));
-            }
-            // arcs not yet applied: carried over, applied when the walk gets here; out of another layer
-            // they keep resolving against that layer (its assets, its namespace for internal arcs)
-            for (int k = 0; k < 2; ++k) {
-                const std::vector<Arc>& from_arcs = k ? src.payloads : src.references;
-                std::vector<Arc>& to_arcs = k ? dp.payloads : dp.references;
-                for (Arc a : from_arcs) {
-                    if (&S != &D && !a.resolved && !S.layer_id.empty()) {
-                        a.asset = a.asset.empty() ? S.layer_id : resolve(S.layer_id, a.asset);
-                        a.resolved = true;
-                    }
-                    to_arcs.push_back(std::move(a));
-                }
-            }
-            for (const auto& kv : src.variant_sel) dp.variant_sel.emplace(kv.first, kv.second);
-            // variant bodies: prim indices of S.  Within one stage they stay valid; from another stage
-            // (a sublayer, a referenced layer) each body subtree is merged into a detached prim of D
-            // at "<dest path>{set=variant}" first, and D's index is kept.  A body D already has for
-            // that variant is the stronger opinion and stays.
-            std::vector<std::pair<std::pair<std::string, std::string>, int>> foreign;
-            for (const auto& kv : src.variant_bodies)
-                for (const auto& v : kv.second) {
-                    if (&S == &D) dp.variant_bodies[kv.first].emplace(v.first, v.second);
-                    else if (!dp.variant_bodies.count(kv.first) || !dp.variant_bodies[kv.first].count(v.first))
-                        foreign.push_back({{kv.first, v.first}, v.second});
-                }
-            const std::string dpath = dp.path;
-            for (const auto& f : foreign) {   // (dp may move from here on)
-                if (f.second <= 0 || (size_t)f.second >= S.prims.size()) continue;
-                const int body = D.add_detached(dpath + "{" + f.first.first + "=" + f.first.second + "}");
-                if (!merge(D, body, S, f.second, from, to)) return false;
-                D.prims[dd].variant_bodies[f.first.first].emplace(f.first.second, body);
-            }
-            for (int c : src.children) {
-                const std::string name = S.prims[c].name;
-                const bool active = S.prims[c].active;
-                const size_t before = D.prims.size();
-                const int dc = D.add_prim(dd, name);
-                if (D.prims.size() > before) D.prims[dc].active = active;
-                work.push_back({dc, c});
-            }
-        }
-        return true;
-    }
-
-    // the prim an arc targets: its path, else the layer's defaultPrim, else its first root prim
-    static int target(const Stage& S, const Arc& a) {
-        if (!a.path.empty()) return S.find(a.path);
-        if (!S.default_prim.empty()) return S.find("/" + S.default_prim);
-        return S.prims[0].children.empty() ? -1 : S.prims[0].children[0];
-    }
-
-    // LIVRPS below local opinions: the selected variants, then references, then payloads.  A
-    // selection whose variant set has no body yet stays: a reference or payload merged later may
-    // bring the set (the common pattern: the referencing prim selects a variant of the asset it
-    // references); its own selection stays the stronger one (merge keeps existing selections).
-    // Each set is composed once.
-    bool apply_arcs(const std::string& id, Stage& L, int p, int depth, bool variants) {
-        std::set<std::string> composed;
-        for (int round = 0; round < kMaxArcDepth; ++round) {
-            Prim& P = L.prims[p];
-            std::vector<int> bodies;
-            for (const auto& kv : P.variant_sel) {
-                if (!variants) break;
-                if (composed.count(kv.first)) continue;
-                auto set = P.variant_bodies.find(kv.first);
-                if (set == P.variant_bodies.end()) continue;
-                auto var = set->second.find(kv.second);
-                if (var == set->second.end()) continue;
-                composed.insert(kv.first);
-                bodies.push_back(var->second);
-            }
-            std::vector<Arc> arcs = P.references;
-            arcs.insert(arcs.end(), P.payloads.begin(), P.payloads.end());
-            P.references.clear();
-            P.payloads.clear();
-            if (bodies.empty() && arcs.empty()) {   // settled (a non-root layer keeps its variants for the stack)
-                if (variants) {
-                    P.variant_sel.clear();
-                    P.variant_bodies.clear();
-                }
-                return true;
-            }
-            for (int b : bodies)
-                if (!merge(L, p, L, b, L.prims[b].path, L.prims[p].path)) return false;
-            // the internal arcs of one round all read this layer's namespace as it stood before the
-            // round's merges (as in USD, where the arcs of one list target the authored namespace,
-            // not each other's results): one snapshot per round, taken before the round's arcs merge
-            // and charged once against the byte budget (thousands of rounds next to one large array
-            // still fail fast instead of copying the layer thousands of times)
-            auto is_internal = [&](const Arc& a) { return a.asset.empty() || (a.resolved && a.asset == id); };
-            std::shared_ptr<const Stage> snapshot;
-            if (std::any_of(arcs.begin(), arcs.end(), is_internal)) {
-                if (!spend(L.prims.size()) || !spend_bytes(stage_bytes(L))) return false;
-                snapshot = std::make_shared<const Stage>(L);
-            }
-            for (const Arc& a : arcs) {
-                if (!spend(1)) return false;
-                std::shared_ptr<const Stage> S;
-                const bool internal = is_internal(a);
-                if (internal) {
-                    S = snapshot;
-                } else if (!(S = load(a.resolved ? a.asset : resolve(id, a.asset), depth + 1))) return false;
-                const int t = target(*S, a);
-                if (t <= 0) return fail("reference target " + (a.path.empty() ? "(default prim)" : a.path) + " not found in " +
-                                        (internal ? id : a.asset));
-                if (internal && t == p) continue;
-                if (!merge(L, p, *S, t, S->prims[t].path, L.prims[p].path)) return false;
-            }
-        }
-        return fail("composition of " + L.prims[p].path + " does not settle");
-    }
-};
-
-}  // namespace
-
-static bool load_stage_impl(const std::string& path, Stage& st, std::vector<PackageFile>& files, std::string& err) {
-    struct stat sb;
-    if (stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode) || (uint64_t)sb.st_size > kMaxLayerBytes) {
-        err = "cannot open " + path + " (not a regular file of at most 2 GiB)";
-        return false;
-    }
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) { err = "cannot open " + path; return false; }
-    std::vector<uint8_t> data;
-    uint8_t buf[1 << 16];
-    size_t k;
-    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + k);
-    std::fclose(f);
-    if (data.size() >= 4 && rd32(data.data()) == 0x04034b50u) {   // .usdz: the first layer is the root
-        if (!read_zip(data.data(), data.size(), files, err)) return false;
-        for (const PackageFile& pf : files) {
-            const size_t dot = pf.name.find_last_of('.');
-            const std::string ext = dot == std::string::npos ? "" : pf.name.substr(dot);
-            if (ext == ".usd" || ext == ".usda" || ext == ".usdc") {
-                if (!parse_layer(pf.data.data(), pf.data.size(), st, err)) return false;
-                st.layer_id = normalize(pf.name);
-                Composer comp(&files);
-                if (!comp.compose(normalize(pf.name), st, 0)) { err = comp.err; return false; }
-                return true;
-            }
-        }
-        err = "usdz package without a USD layer";
-        return false;
-    }
-    if (!parse_layer(data.data(), data.size(), st, err)) return false;
-    st.layer_id = path;
-    Composer comp(nullptr);
-    if (!comp.compose(path, st, 0)) { err = comp.err; return false; }
-    return true;
-}
-
-// Asset bytes are untrusted: a file that asks for more memory than the process has fails the load
-// (RT_ERR_IO at rt_scene_add_usd) instead of letting std::bad_alloc cross the C-ABI.
-bool load_stage(const std::string& path, Stage& st, std::vector<PackageFile>& files, std::string& err) {
-    try {
-        return load_stage_impl(path, st, files, err);
-    } catch (const std::bad_alloc&) {
-        err = "out of memory while reading " + path;
-    } catch (const std::exception& e) {
-        err = std::string("error while reading ") + path + ": " + e.what();
-    }
-    st = Stage();
-    files.clear();
-    return false;
 }
 
 }  // namespace usd

@@ -115,7 +115,7 @@ bool read_zip(const uint8_t* data, size_t n, std::vector<PackageFile>& files, st
 // .usdz / .usda / .usdc by content; `files` receives a package's entries (empty for a bare layer)
 bool load_stage(const std::string& path, Stage& st, std::vector<PackageFile>& files, std::string& err);
 
-// LZ4 block and TfFastCompression framing (exposed for tests via the C-ABI debug hook)
+// one LZ4 block (the crate reader's sections and arrays)
 bool lz4_block_decode(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_n);
 
 }  // namespace usd

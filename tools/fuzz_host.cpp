@@ -1,6 +1,6 @@
 // Mutation fuzzer for the host-side readers of untrusted asset bytes: the USD text / crate / zip
-// readers behind rt_scene_add_usd (rt_usd.cpp + the scene mapping in rt_scene.cpp) and the PNG
-// decoder (rt_texture.cpp) and the OBJ reader (rt_scene.cpp).  Built with AddressSanitizer + UBSan by tools/fuzz_host.sh; every
+// readers behind rt_scene_add_usd (rt_usda.cpp, rt_usd.cpp, rt_usdz.cpp, rt_usd_compose.cpp + the scene
+// mapping in rt_scene_usd.cpp), the PNG decoder (rt_texture.cpp) and the OBJ reader (rt_scene_obj.cpp).  Built with AddressSanitizer + UBSan by tools/fuzz_host.sh; every
 // input must end in RT_OK or an error status, never in a sanitizer report or a crash.
 //
 //   fuzz_host <usda|usdc|usdz|png|obj> <seed file> <iterations> <rng seed>
