@@ -439,6 +439,81 @@ rt_status rt_trace_closest_on(rt_ctx* ctx, const rt_ray* rays, uint32_t n, rt_ra
 rt_status rt_trace_any_on(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t* occluded, void* hip_stream);
 rt_status rt_get_query_stats(rt_ctx* ctx, rt_query_stats* out);
 
+/* ---- Surface queries: a ray and its hit record resolved into shading inputs ---------------------
+ * What a Metal kernel does after `intersector.intersect`: read the Resource buffers for the vertex
+ * normals, the UVs, the instance matrix, the material and its maps (Raytracing.metal:324-339,
+ * :391-456, :492-504).  Here those buffers are the library's, in its own layouts, so the library
+ * resolves the hit: rt_resolve_hits turns `n` rays (the ones that were traced) and their
+ * rt_ray_hit records into one rt_surface and, unless `materials` is NULL, one
+ * rt_surface_material each.  Every float is the one the renderer's own shading forms at that hit,
+ * bit for bit (the same expressions in the same order; with the G-buffer on, a frame's normal,
+ * albedo and roughness planes equal the records of its sample-0 primary rays).  With
+ * rt_trace_closest, the caller's own ray generation and rt_trace_any this is a complete
+ * user-side integrator (ambient occlusion, lidar, visibility baking).
+ *
+ * `rays`, `hits`, `surfaces` and `materials` are DEVICE pointers; the call enqueues one kernel
+ * launch (one thread per record, no host wait).  rt_surface is 64 B and written as four 16-B
+ * words, rt_surface_material 48 B as three. */
+typedef struct rt_surface {          /* 64 B */
+    float position[3];       /* origin + direction * t (the renderer's P, :336) */
+    float t;                 /* copied from the hit */
+    float normal[3];         /* the renderer's Ng: the interpolated vertex normal through the instance
+                                4x3, normalised; -direction where the object-space normal is shorter
+                                than 1e-10 (:391-397) */
+    float u;                 /* texture coordinate, see RT_SURFACE_HAS_UV */
+    float shading_normal[3]; /* Ng, or the normal-mapped normal (:492-504) */
+    float v;
+    uint32_t triangle;       /* copied from the hit */
+    uint32_t mesh;           /* copied from the hit */
+    uint32_t submesh;        /* copied from the hit */
+    uint32_t flags;          /* RT_SURFACE_* */
+} rt_surface;
+
+typedef struct rt_surface_material { /* 48 B */
+    float base_color[3];     /* baseColor x the base-colour map */
+    float opacity;           /* clamp(opacity x the opacity map, 0, 1) */
+    float emission[3];       /* emission; an emission map replaces it (:453-456) */
+    float ior;               /* max(refractionIndex, 1) */
+    float roughness;         /* 1 without a roughness map, else the map's value, unclamped */
+    float metallic;          /* 0 without a metallic map, else the map's value, unclamped */
+    uint32_t texture_flags;  /* Material.textureFlags */
+    uint32_t slot;           /* material slot: mesh * (largest submesh count of the scene) + submesh */
+} rt_surface_material;
+RT_STATIC_ASSERT(sizeof(rt_surface) == 64, "rt_surface is four 16-B words");
+RT_STATIC_ASSERT(sizeof(rt_surface_material) == 48, "rt_surface_material is three 16-B words");
+
+#define RT_SURFACE_HAS_UV       1u  /* the submesh has a bound map and (u, v) is the coordinate it is
+                                        sampled at (after the v flip, :417); otherwise u = v = 0 */
+#define RT_SURFACE_BACKFACE      2u  /* dot(direction, normal) > 0 */
+#define RT_SURFACE_NORMAL_MAPPED 4u  /* the tangent basis was valid and the normal map was applied */
+#define RT_SURFACE_TRANSMISSIVE  8u  /* the renderer's glass test: opacity < 0.999 || ior > 1.01 (:517) */
+
+/* Semantics:
+ *  - Hit data is used as given: t, u and v of the hit are not re-derived, so a caller may compact,
+ *    reorder or edit hit records (with their rays).  `triangle` selects the geometry; mesh and
+ *    submesh are copied through, the matrix and the material are looked up by the triangle's own
+ *    instance and submesh.
+ *  - A hit record whose `triangle` is RT_MISS, or at or above the scene's triangle count, is a
+ *    miss and indexes nothing.  Its surface is position (0, 0, 0), t = INFINITY, zero normals and
+ *    u, v, triangle = mesh = submesh = RT_MISS, flags 0; its material record is all zero.
+ *  - materials == NULL skips that record and the base-colour, roughness, metallic and emission
+ *    loads and samples.  The surface record is the same either way: the opacity (with its map)
+ *    and the refraction index are read in both forms, RT_SURFACE_TRANSMISSIVE needs them.
+ *  - Geometry seen, ordering against updates, rt_wait and rt_destroy: exactly as for
+ *    rt_trace_closest above (the generation the next frame would read, after the update stream's
+ *    work so far; updates first wait for pending resolves).  Frames rendered with resolves
+ *    interleaved are bit-identical to frames rendered without.
+ *  - The plain form runs on the context's stream, the _on form on `hip_stream` exactly as given.
+ *    Back-to-back resolves and traces, also on different streams, need no host wait.
+ *  - Errors: a NULL rays / hits / surfaces pointer with n > 0, or any pointer not 16-byte aligned:
+ *    RT_ERR_INVALID_ARG.  Before a BVH build: RT_ERR_STATE.  n == 0: RT_OK, nothing is launched.
+ *  - Statistics: a resolve is NOT folded into rt_query_stats; that struct (its last-query fields
+ *    and its totals) describes traces only. */
+rt_status rt_resolve_hits(rt_ctx* ctx, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
+                          rt_surface_material* materials);
+rt_status rt_resolve_hits_on(rt_ctx* ctx, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
+                             rt_surface_material* materials, void* hip_stream);
+
 /* Library build identification (kernel code object arch etc). */
 const char* rt_version(void);
 
@@ -450,6 +525,13 @@ const char* rt_version(void);
 rt_status rt_debug_trace_host(const rt_scene_desc* scene, const float* rays, const float* tmax, uint32_t n,
                               int32_t any, float* t, uint32_t* id, float* u, float* v, uint32_t* nodes,
                               uint32_t* tris);
+
+/* Test hook (host only, no device): rt_resolve_hits over a scene description, by the code the
+ * kernel runs, compiled for the host.  All pointers are HOST pointers here; `materials` may be
+ * NULL.  The scene is checked as rt_scene_upload checks it.  Any material, normal maps and
+ * base-colour maps included. */
+rt_status rt_debug_resolve_host(const rt_scene_desc* scene, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n,
+                                rt_surface* surfaces, rt_surface_material* materials);
 
 #ifdef __cplusplus
 }

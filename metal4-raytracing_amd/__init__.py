@@ -123,6 +123,25 @@ def debug_trace_host(scene, origins, dirs, tmax=None, any_hit=False):
     return out
 
 
+def debug_resolve_host(scene, rays, hits, material=True):
+    """Test hook: rt_resolve_hits on the host (rt_debug_resolve_host), over a scene description.
+    rays: (n, 8) float32 rt_ray records (Renderer.make_rays); hits: a Hits object or its (n, 8)
+    buffer.  Returns a Surface of numpy arrays."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    h = np.ascontiguousarray(hits.buffer if isinstance(hits, Hits) else hits).reshape(-1, 8)
+    if h.dtype != np.float32:
+        raise ValueError("hits must be float32 (n, 8) rt_ray_hit records")
+    n = r.shape[0]
+    if h.shape[0] != n:
+        raise ValueError(f"{n} rays but {h.shape[0]} hit records")
+    surf = np.empty((n, 16), np.float32)
+    mat = np.empty((n, 12), np.float32) if material else None
+    d_ = scene.desc()
+    _check(lib().rt_debug_resolve_host(C.byref(d_), r.ctypes.data, h.ctypes.data, n, surf.ctypes.data,
+                                       mat.ctypes.data if material else None))
+    return Surface(surf, surf.view(np.int32), mat, mat.view(np.int32) if material else None)
+
+
 def glass_override():
     o = MaterialOverride()
     lib().rt_material_override_glass(C.byref(o))
@@ -310,6 +329,32 @@ class Hits:
         return self.buffer.shape[0]
 
 
+class Surface:
+    """Results of Renderer.resolve: `buffer` holds the (n, 16) rt_surface records, `material_buffer`
+    the (n, 12) rt_surface_material records (None with material=False), and the fields are views of
+    them.  float32: position (n, 3), t, normal (n, 3), uv (n, 2), shading_normal (n, 3) and, with
+    materials, base_color (n, 3), opacity, emission (n, 3), ior, roughness, metallic.  int32:
+    triangle, mesh, submesh (-1 on a miss), flags (RT_SURFACE_* bits) and, with materials,
+    texture_flags, slot.  Torch tensors on the device path, numpy arrays on the host path."""
+
+    HAS_UV, BACKFACE, NORMAL_MAPPED, TRANSMISSIVE = (_abi.RT_SURFACE_HAS_UV, _abi.RT_SURFACE_BACKFACE,
+                                                     _abi.RT_SURFACE_NORMAL_MAPPED, _abi.RT_SURFACE_TRANSMISSIVE)
+
+    def __init__(self, buffer, as_int, material_buffer=None, material_as_int=None):
+        self.buffer, self.material_buffer = buffer, material_buffer
+        self.position, self.t, self.normal = buffer[:, 0:3], buffer[:, 3], buffer[:, 4:7]
+        self.uv, self.shading_normal = buffer[:, 7:12:4], buffer[:, 8:11]   # u and v close words 1 and 2
+        self.triangle, self.mesh, self.submesh, self.flags = (as_int[:, k] for k in (12, 13, 14, 15))
+        if material_buffer is not None:
+            m = material_buffer
+            self.base_color, self.opacity, self.emission, self.ior = m[:, 0:3], m[:, 3], m[:, 4:7], m[:, 7]
+            self.roughness, self.metallic = m[:, 8], m[:, 9]
+            self.texture_flags, self.slot = material_as_int[:, 10], material_as_int[:, 11]
+
+    def __len__(self):
+        return self.buffer.shape[0]
+
+
 class Renderer:
     """Renderer.swift for the hot path: owns a device context, the uniforms and the frame index.
 
@@ -479,6 +524,62 @@ class Renderer:
             res = out.cpu().numpy()
             return res if any_hit else Hits(res, res.view(np.int32))
         return out if any_hit else Hits(out, out.view(torch.int32))
+
+    def resolve(self, rays, hits, material=True, out=None, stream=None):
+        """rt_resolve_hits: turns (n, 8) rays and their closest-hit records (a Hits object or its
+        (n, 8) buffer) into surface and material records: what the renderer itself would shade at
+        each hit, bit for bit, against the geometry the next draw() would see.
+
+        Device path (`rays` is a torch tensor; so is the hit buffer): enqueued on `stream` (as in
+        trace: 0 = HIP's null stream, None = the renderer's) without a host wait.  `out` is an
+        (n, 16) float32 tensor, or a pair of it and an (n, 12) one; with material=False no material
+        record is written.  Host path (`rays` is a host array): staged through torch, waited for,
+        returned as numpy.  Returns a Surface."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        hb = hits.buffer if isinstance(hits, Hits) else hits
+        host = not isinstance(rays, torch.Tensor)
+        if host:
+            r = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 8)).to(dev)
+            if isinstance(hb, torch.Tensor):
+                raise ValueError("rays on the host but hits on the device")
+            hb = np.ascontiguousarray(hb)
+            if hb.dtype != np.float32 or hb.ndim != 2 or hb.shape[1] != 8:
+                raise ValueError("hits must be float32 (n, 8) rt_ray_hit records")
+            h = torch.from_numpy(hb).to(dev)
+        else:
+            r, h = rays, hb
+            for name, x in (("rays", r), ("hits", h)):
+                if (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 8
+                        or not x.is_contiguous() or x.device != dev):
+                    raise ValueError(f"{name} must be a contiguous float32 (n, 8) tensor on {dev}")
+        n = r.shape[0]
+        if h.shape[0] != n:
+            raise ValueError(f"{n} rays but {h.shape[0]} hit records")
+        surf, mat = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
+        for name, x, cols in (("surfaces", surf, 16), ("materials", mat, 12)):
+            if x is not None and (not isinstance(x, torch.Tensor) or tuple(x.shape) != (n, cols) or x.dtype != torch.float32
+                                  or not x.is_contiguous() or x.device != dev):
+                raise ValueError(f"out {name} must be a contiguous float32 ({n}, {cols}) tensor on {dev}")
+        if mat is not None and not material:
+            raise ValueError("a materials tensor was given with material=False")
+        if surf is None:
+            surf = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        if material and mat is None:
+            mat = torch.empty((n, 12), dtype=torch.float32, device=dev)
+        if host:
+            torch.cuda.current_stream(dev).synchronize()   # the staging copies and the allocator's stream
+        args = (self._ctx, C.c_void_p(r.data_ptr()), C.c_void_p(h.data_ptr()), n, C.c_void_p(surf.data_ptr()),
+                C.c_void_p(mat.data_ptr()) if material else None)
+        if stream is None:
+            _check(lib().rt_resolve_hits(*args), self._ctx)
+        else:
+            _check(lib().rt_resolve_hits_on(*args, C.c_void_p(stream)), self._ctx)
+        if host:
+            self.wait()
+            s, m = surf.cpu().numpy(), mat.cpu().numpy() if material else None
+            return Surface(s, s.view(np.int32), m, m.view(np.int32) if material else None)
+        return Surface(surf, surf.view(torch.int32), mat, mat.view(torch.int32) if material else None)
 
     def query_stats(self):
         """rt_get_query_stats (waits for pending queries): the last query and the running totals."""

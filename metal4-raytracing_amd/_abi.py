@@ -208,6 +208,20 @@ class RayHit(C.Structure):  # rt_ray_hit: 32 B, two 16-B words
                 ("submesh", C.c_uint32), ("primitive", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Surface(C.Structure):  # rt_surface: 64 B, four 16-B words
+    _fields_ = [("position", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("u", C.c_float),
+                ("shading_normal", C.c_float * 3), ("v", C.c_float), ("triangle", C.c_uint32), ("mesh", C.c_uint32),
+                ("submesh", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SurfaceMaterial(C.Structure):  # rt_surface_material: 48 B, three 16-B words
+    _fields_ = [("base_color", C.c_float * 3), ("opacity", C.c_float), ("emission", C.c_float * 3), ("ior", C.c_float),
+                ("roughness", C.c_float), ("metallic", C.c_float), ("texture_flags", C.c_uint32), ("slot", C.c_uint32)]
+
+
+RT_SURFACE_HAS_UV, RT_SURFACE_BACKFACE, RT_SURFACE_NORMAL_MAPPED, RT_SURFACE_TRANSMISSIVE = 1, 2, 4, 8
+
+
 class QueryStats(C.Structure):  # rt_query_stats
     _fields_ = [
         ("rays", C.c_uint64),
@@ -273,7 +287,8 @@ EXPORTED_SYMBOLS = [
     "rt_pack_tiles_host", "rt_unpack_tiles_host",
     "rt_set_counting", "rt_set_device_spans", "rt_set_graphs", "rt_get_stats", "rt_set_tuning", "rt_get_tuning",
     "rt_trace_closest", "rt_trace_any", "rt_trace_closest_on", "rt_trace_any_on", "rt_get_query_stats",
-    "rt_version", "rt_debug_trace_host",
+    "rt_resolve_hits", "rt_resolve_hits_on",
+    "rt_version", "rt_debug_trace_host", "rt_debug_resolve_host",
     # rt_scene.h
     "rt_material_override_glass", "rt_scene_new", "rt_scene_free", "rt_scene_last_error",
     "rt_scene_add_obj", "rt_scene_add_usd", "rt_scene_add_procedural", "rt_scene_set_lights", "rt_scene_set_light_intensity",
@@ -329,6 +344,9 @@ def declare(lib):
         "rt_trace_closest_on": (st, [vp, vp, C.c_uint32, vp, vp]),
         "rt_trace_any_on": (st, [vp, vp, C.c_uint32, vp, vp]),
         "rt_get_query_stats": (st, [vp, P(QueryStats)]),
+        "rt_resolve_hits": (st, [vp, vp, vp, C.c_uint32, vp, vp]),
+        "rt_resolve_hits_on": (st, [vp, vp, vp, C.c_uint32, vp, vp, vp]),
+        "rt_debug_resolve_host": (st, [P(SceneDesc), vp, vp, C.c_uint32, vp, vp]),
         "rt_version": (C.c_char_p, []),
         "rt_debug_trace_host": (st, [P(SceneDesc), P(C.c_float), P(C.c_float), C.c_uint32, C.c_int32, P(C.c_float),
                                      P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32)]),

@@ -1,8 +1,10 @@
 // rt_api_query.cpp — device ray queries: rt_trace_closest / rt_trace_any enqueue one rq_trace
 // launch (rt_query.hip) over the caller's device rays against the geometry generation the next
 // frame would read, and rt_get_query_stats reports them.  The replacement of Metal's
-// `intersector.intersect` called outside raytracingKernel.  Queries share nothing writable with
-// frames: their counters, events and statistics are their own (QuerySlot, rt_ctx.h).
+// `intersector.intersect` called outside raytracingKernel.  rt_resolve_hits enqueues one
+// rq_resolve launch that turns rays and their hit records into surface and material records, by
+// the same generation rule.  Queries share nothing writable with frames: their counters, events
+// and statistics are their own (QuerySlot, rt_ctx.h).
 #include <algorithm>
 #include <cstring>
 
@@ -18,6 +20,7 @@ rt_status harvest_query(rt_ctx* c, int k) {
     if (!q.pending) return RT_OK;
     q.pending = false;
     HIPC(c, hipEventSynchronize(q.done));
+    if (q.resolve) return RT_OK;   // a surface query: waited for, not part of rt_query_stats
     float ms = 0.0f;
     HIPC(c, hipEventElapsedTime(&ms, q.ev0, q.ev1));
     const unsigned long long* hc = q.h_counters.get();
@@ -56,8 +59,40 @@ rt_status ensure_query_slot(rt_ctx* c, QuerySlot& q) {
     return RT_OK;
 }
 
-// own_stream: the ctx stream (rt_trace_closest / rt_trace_any); otherwise `stream` as the caller
-// gave it, the null stream included
+// What every query does before its launch: takes the oldest slot (its previous query, kQuerySlots
+// back, has finished) and makes `stream` wait for the geometry the next frame would read: the
+// generation updates since the newest frame went into (after the update stream's work so far),
+// else the one frames read (after the event of the flip that made it current).  Returns that
+// generation; the caller launches on `stream`, records q->done and calls commit_query.
+// own_stream: the ctx stream (the plain entry points); otherwise `stream` as the caller gave it,
+// the null stream included.
+rt_status begin_query(rt_ctx* c, hipStream_t& stream, bool own_stream, QuerySlot*& q, const Geo*& geo) {
+    HIPC(c, hipSetDevice(c->device));
+    if (own_stream) stream = c->stream;
+    q = &c->qslot[c->qnext];
+    rt_status st = harvest_query(c, c->qnext);
+    if (!st) st = ensure_query_slot(c, *q);
+    if (st) return st;
+    if (c->ring.gdirty) {
+        if (!c->q_uev) HIPC(c, c->q_uev.create(hipEventDisableTiming));
+        HIPC(c, hipEventRecord(c->q_uev, c->ustream));
+        HIPC(c, hipStreamWaitEvent(stream, c->q_uev, 0));
+    } else if (c->uev_valid) {
+        HIPC(c, hipStreamWaitEvent(stream, c->uev, 0));
+    }
+    geo = &c->geo[c->ring.write_gen()];
+    return RT_OK;
+}
+
+// After the launch: `done` marks its end for updates, rt_wait and rt_destroy (drain_queries).
+rt_status commit_query(rt_ctx* c, QuerySlot& q, hipStream_t stream, bool resolve) {
+    HIPC(c, hipEventRecord(q.done, stream));
+    q.pending = true;
+    q.resolve = resolve;
+    c->qnext = (c->qnext + 1) % kQuerySlots;
+    return RT_OK;
+}
+
 rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, hipStream_t stream, bool own_stream) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (n > 0) {
@@ -67,23 +102,11 @@ rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, 
     }
     if (!c->bvh_ready) FAIL(c, RT_ERR_STATE, "ray query before rt_bvh_build");
     if (n == 0) return RT_OK;
-    HIPC(c, hipSetDevice(c->device));
-    if (own_stream) stream = c->stream;
-    QuerySlot& q = c->qslot[c->qnext];
-    rt_status st = harvest_query(c, c->qnext);   // the slot's previous query (kQuerySlots back) has finished
-    if (!st) st = ensure_query_slot(c, q);
-    if (st) return st;
-    // the geometry the next frame would read: the generation updates since the newest frame went
-    // into (after the update stream's work so far), else the one frames read (after the event of
-    // the flip that made it current)
-    if (c->ring.gdirty) {
-        if (!c->q_uev) HIPC(c, c->q_uev.create(hipEventDisableTiming));
-        HIPC(c, hipEventRecord(c->q_uev, c->ustream));
-        HIPC(c, hipStreamWaitEvent(stream, c->q_uev, 0));
-    } else if (c->uev_valid) {
-        HIPC(c, hipStreamWaitEvent(stream, c->uev, 0));
-    }
-    const Geo& geo = c->geo[c->ring.write_gen()];
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    QuerySlot& q = *qp;
+    const Geo& geo = *gp;
     DevScene S;
     std::memset(&S, 0, sizeof S);   // the traversal reads the tree, the triangles and tri_info only
     S.tris = (const float*)geo[Geo::tris].p;
@@ -109,12 +132,52 @@ rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, 
     HIPC(c, hipEventRecord(q.ev1, stream));
     HIPC(c, hipMemcpyAsync(q.h_counters, q.state.p, sizeof(unsigned long long) * kCounterWords, hipMemcpyDeviceToHost,
                            stream));
-    HIPC(c, hipEventRecord(q.done, stream));
-    q.pending = true;
     q.any = any;
     q.blocks = blocks;
-    c->qnext = (c->qnext + 1) % kQuerySlots;
-    return RT_OK;
+    return commit_query(c, q, stream, false);
+}
+
+rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
+                  rt_surface_material* materials, hipStream_t stream, bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (n > 0) {
+        if (!rays || !hits || !surfaces) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+        if (((uintptr_t)rays | (uintptr_t)hits | (uintptr_t)surfaces | (uintptr_t)materials) & 15u)
+            FAIL(c, RT_ERR_INVALID_ARG, "rays, hits, surfaces and materials must be 16-byte aligned");
+    }
+    if (!c->bvh_ready) FAIL(c, RT_ERR_STATE, "surface query before rt_bvh_build");
+    if (n == 0) return RT_OK;
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    const Geo& geo = *gp;
+    DevScene S;
+    std::memset(&S, 0, sizeof S);   // surface_eval reads the shading streams only, not the tree
+    S.pos = (const float4*)geo[Geo::pos].p;
+    S.tri_nrm = (const float4*)geo[Geo::tri_nrm].p;
+    S.inst = (const float*)geo[Geo::inst].p;
+    S.materials = (const Material*)c->d_mat.p;
+    S.max_submeshes = c->max_sub;
+    S.num_materials = (int)c->h_mat.size();
+    S.num_tris = (int)c->num_tris;
+    S.textured = c->textured ? 1 : 0;
+    if (c->textured) {
+        S.tex_texels = (const uchar4*)c->d_tex_texels.p;
+        S.tex_info = (const uint4*)c->d_tex_info.p;
+        S.mat_tex = (const int4*)c->d_mat_tex.p;
+        S.uv = (const float2*)c->d_uv.p;
+        S.tex_lut = (const float*)c->d_tex_lut.p;
+    }
+    RsParams P;
+    P.rays = (const float4*)rays;
+    P.hits = (const float4*)hits;
+    P.surfaces = (float4*)surfaces;
+    P.materials = (float4*)materials;
+    P.n = n;
+    const unsigned blocks = std::min(resolve_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u);
+    launch_resolve(S, P, blocks, stream);
+    HIPC(c, hipGetLastError());
+    return commit_query(c, *qp, stream, true);
 }
 }  // namespace
 
@@ -140,6 +203,16 @@ rt_status rt_trace_closest_on(rt_ctx* c, const rt_ray* rays, uint32_t n, rt_ray_
 
 rt_status rt_trace_any_on(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t* occluded, void* stream) {
     return trace(c, rays, n, occluded, true, (hipStream_t)stream, false);
+}
+
+rt_status rt_resolve_hits(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
+                          rt_surface_material* materials) {
+    return resolve(c, rays, hits, n, surfaces, materials, nullptr, true);
+}
+
+rt_status rt_resolve_hits_on(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
+                             rt_surface_material* materials, void* stream) {
+    return resolve(c, rays, hits, n, surfaces, materials, (hipStream_t)stream, false);
 }
 
 rt_status rt_get_query_stats(rt_ctx* c, rt_query_stats* out) {

@@ -8,6 +8,7 @@
 #include <exception>
 
 #include "rt_ctx.h"
+#include "rt_scene_host.h"
 
 using namespace rt;
 
@@ -58,33 +59,6 @@ std::vector<float> slot_ordered_tris(const std::vector<float>& world, const std:
     return tris;
 }
 
-// A scene description flattened mesh by mesh: positions and normals with every mesh's vertices
-// after the previous one's, triangles as (three vertex ids, mesh << 8 | submesh), 12 floats of
-// transform per mesh.  nrm may be null.
-void flatten_scene(const rt_scene_desc* sd, std::vector<float4>& pos, std::vector<float4>* nrm,
-                   std::vector<uint4>& tri_info, std::vector<float>& inst) {
-    pos.clear();
-    tri_info.clear();
-    if (nrm) nrm->clear();
-    inst.assign(12 * (size_t)sd->mesh_count, 0.0f);
-    for (uint32_t m = 0; m < sd->mesh_count; ++m) {
-        const rt_mesh_desc& md = sd->meshes[m];
-        const uint32_t vbase = (uint32_t)pos.size();
-        std::memcpy(&inst[12 * (size_t)m], &md.transform, 48);
-        for (uint32_t v = 0; v < md.vertex_count; ++v) {
-            const rt_float3& p = md.positions[v];
-            pos.push_back(make_float4(p.x, p.y, p.z, 0.0f));
-            if (nrm) nrm->push_back(make_float4(md.normals[v].x, md.normals[v].y, md.normals[v].z, 0.0f));
-        }
-        for (uint32_t s = 0; s < md.submesh_count; ++s) {
-            const rt_submesh_desc& sm = md.submeshes[s];
-            for (uint32_t k = 0; k < sm.index_count / 3; ++k)
-                tri_info.push_back(make_uint4(vbase + sm.indices[3 * k + 0], vbase + sm.indices[3 * k + 1],
-                                              vbase + sm.indices[3 * k + 2], (m << 8) | s));
-        }
-    }
-}
-
 // Before a geometry update: the first one after a frame switches to the next generation, once the
 // frames still reading it have finished, seeded with a copy of the current one (on the update
 // stream; frames keep reading the current generation meanwhile).  Every entry point that writes
@@ -109,98 +83,19 @@ rt_status begin_update(rt_ctx* c) {
     return RT_OK;
 }
 
-// Texture path: the texel pool, its table, every material slot's texture
-// ids and the per-vertex UVs (Model.vertexDescriptor's zero default when a mesh has none,
-// Model.swift:329-333).  Nothing is uploaded for an untextured scene.
+// The texture tables of a textured scene (build_tex_tables, rt_scene_host.h).  Nothing is
+// uploaded for an untextured scene.
 rt_status upload_textures(rt_ctx* c, const rt_scene_desc* sd) {
-    const uint32_t slots = (uint32_t)c->max_sub * sd->mesh_count;
-    std::vector<int4> mt(2 * (size_t)slots, make_int4(0, -1, -1, -1));
-    bool textured = false;
-    for (uint32_t m = 0; m < sd->mesh_count; ++m)
-        for (uint32_t s = 0; s < sd->meshes[m].submesh_count; ++s) {
-            const rt_submesh_desc& sm = sd->meshes[m].submeshes[s];
-            uint32_t flags = sm.material.textureFlags & ~(1u << 4);   // ENABLE_AO = 0
-            if (!flags) continue;
-            textured = true;
-            int t[8];
-            for (int k = 0; k < 8; ++k) t[k] = (k < RT_TEXTURE_SLOTS && (flags >> k & 1u)) ? sm.textures[k] : -1;
-            const size_t slot = (size_t)m * c->max_sub + s;
-            mt[2 * slot] = make_int4((int)flags, t[0], t[1], t[2]);
-            mt[2 * slot + 1] = make_int4(t[3], t[4], t[5], t[6]);
-        }
-    c->textured = textured;
-    if (!textured) return RT_OK;
-    std::vector<uint4> info(sd->texture_count);
-    std::vector<uint8_t> texels;
-    uint64_t off = 0;
-    for (uint32_t t = 0; t < sd->texture_count; ++t) {
-        const rt_texture_desc& td = sd->textures[t];
-        info[t] = make_uint4((uint32_t)off, td.width, td.height, 0u);
-        off += (uint64_t)td.width * td.height;
-    }
-    texels.resize(off * 4);
-    for (uint32_t t = 0; t < sd->texture_count; ++t)
-        std::memcpy(&texels[4 * (size_t)info[t].x], sd->textures[t].rgba8, 4 * (size_t)info[t].y * info[t].z);
-    std::vector<float2> uv(c->num_verts, make_float2(0.0f, 0.0f));
-    uint32_t vbase = 0;
-    for (uint32_t m = 0; m < sd->mesh_count; ++m) {
-        const rt_mesh_desc& md = sd->meshes[m];
-        if (md.uvs)
-            for (uint32_t v = 0; v < md.vertex_count; ++v) uv[vbase + v] = make_float2(md.uvs[v].x, md.uvs[v].y);
-        vbase += md.vertex_count;
-    }
-    // texel byte -> float: [0, 256) linear b / 255, [256, 512) sRGB EOTF (MTKTextureLoader .SRGB)
-    float lut[512];
-    for (int b = 0; b < 256; ++b) {
-        const double v = b / 255.0;
-        lut[b] = (float)v;
-        lut[256 + b] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4));
-    }
+    TexTables T;
+    build_tex_tables(sd, c->max_sub, c->num_verts, T);
+    c->textured = T.textured;
+    if (!T.textured) return RT_OK;
     rt_status st;
-    if ((st = dev_upload(c, c->d_tex_texels, texels.data(), texels.size()))) return st;
-    if ((st = dev_upload(c, c->d_tex_info, info.data(), info.size() * sizeof(uint4)))) return st;
-    if ((st = dev_upload(c, c->d_mat_tex, mt.data(), mt.size() * sizeof(int4)))) return st;
-    if ((st = dev_upload(c, c->d_uv, uv.data(), uv.size() * sizeof(float2)))) return st;
-    if ((st = dev_upload(c, c->d_tex_lut, lut, sizeof lut))) return st;
-    return RT_OK;
-}
-
-// What rt_scene_upload accepts; the scene's sizes on success.
-rt_status validate_scene(rt_ctx* c, const rt_scene_desc* sd, int& max_sub, uint64_t& nv, uint64_t& nt) {
-    if (sd->mesh_count == 0) FAIL(c, RT_ERR_INVALID_ARG, "scene has no meshes");
-    if (sd->light_count == 0 || !sd->lights) FAIL(c, RT_ERR_INVALID_ARG, "scene has no lights");
-    if (sd->mesh_count >= (1u << 24)) FAIL(c, RT_ERR_UNSUPPORTED, "too many meshes");
-    max_sub = 1;
-    nv = nt = 0;
-    for (uint32_t m = 0; m < sd->mesh_count; ++m) {
-        const rt_mesh_desc& md = sd->meshes[m];
-        if (!md.positions || !md.normals) FAIL(c, RT_ERR_INVALID_ARG, "mesh without positions/normals");
-        if (md.submesh_count == 0 || !md.submeshes) FAIL(c, RT_ERR_INVALID_ARG, "mesh without submeshes");
-        if (md.submesh_count > 256) FAIL(c, RT_ERR_UNSUPPORTED, "more than 256 submeshes in a mesh");
-        if (md.joint_count && (!md.joint_indices || !md.joint_weights)) FAIL(c, RT_ERR_INVALID_ARG, "skinned mesh without joint streams");
-        max_sub = std::max(max_sub, (int)md.submesh_count);
-        nv += md.vertex_count;
-        for (uint32_t s = 0; s < md.submesh_count; ++s) {
-            const rt_submesh_desc& sm = md.submeshes[s];
-            if (sm.index_count % 3) FAIL(c, RT_ERR_INVALID_ARG, "index count not a multiple of 3");
-            if (sm.index_count && !sm.indices) FAIL(c, RT_ERR_INVALID_ARG, "null indices");
-            for (int k = 0; k < RT_TEXTURE_SLOTS; ++k)
-                if (k != 4 && (sm.material.textureFlags >> k & 1u) &&   // the AO slot is never sampled
-                    (sm.textures[k] < 0 || (uint32_t)sm.textures[k] >= sd->texture_count || !sd->textures))
-                    FAIL(c, RT_ERR_INVALID_ARG, "textured material without a valid texture for a flagged slot");
-            for (uint32_t i = 0; i < sm.index_count; ++i)
-                if (sm.indices[i] >= md.vertex_count) FAIL(c, RT_ERR_INVALID_ARG, "index out of range");
-            nt += sm.index_count / 3;
-        }
-    }
-    if (nt >= (1ull << 31) || nv >= (1ull << 32)) FAIL(c, RT_ERR_UNSUPPORTED, "scene too large");
-    uint64_t ntexels = 0;
-    for (uint32_t t = 0; t < sd->texture_count; ++t) {
-        const rt_texture_desc& td = sd->textures[t];
-        if (!td.rgba8 || td.width == 0 || td.height == 0) FAIL(c, RT_ERR_INVALID_ARG, "bad texture");
-        ntexels += (uint64_t)td.width * td.height;
-    }
-    if (ntexels >= (1ull << 32)) FAIL(c, RT_ERR_UNSUPPORTED, "texture pool above 2^32 texels");
+    if ((st = dev_upload(c, c->d_tex_texels, T.texels.data(), T.texels.size()))) return st;
+    if ((st = dev_upload(c, c->d_tex_info, T.info.data(), T.info.size() * sizeof(uint4)))) return st;
+    if ((st = dev_upload(c, c->d_mat_tex, T.mat_tex.data(), T.mat_tex.size() * sizeof(int4)))) return st;
+    if ((st = dev_upload(c, c->d_uv, T.uv.data(), T.uv.size() * sizeof(float2)))) return st;
+    if ((st = dev_upload(c, c->d_tex_lut, T.lut, sizeof T.lut))) return st;
     return RT_OK;
 }
 

@@ -62,8 +62,8 @@ struct Geo {
     const rt::DevBuf& operator[](Buf b) const { return buf[b]; }
 };
 
-// One device ray query in flight (rt_trace_closest / rt_trace_any): the launch's own device state
-// (chunk counters and statistics, rt_kernels.h RqParams::state), its pinned copy and its events.
+// One device ray query in flight (rt_trace_closest / rt_trace_any / rt_resolve_hits): the launch's
+// own device state (chunk counters and statistics, rt_kernels.h RqParams::state), its pinned copy and its events.
 // Queries rotate over kQuerySlots of these, so launches that may overlap (other streams) share no
 // counter; a slot is reused once its previous query has finished (harvest_query).
 constexpr int kQuerySlots = 4;
@@ -72,6 +72,7 @@ struct QuerySlot {
     rt::Pinned<unsigned long long> h_counters;
     rt::Event ev0, ev1, done;   // around the launch (timing); after the counters' copy
     bool pending = false, any = false;
+    bool resolve = false;       // rt_resolve_hits took the slot: only `done` is used, nothing is folded
     uint32_t blocks = 0;        // the launch's grid
 };
 

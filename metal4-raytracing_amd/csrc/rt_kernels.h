@@ -139,6 +139,20 @@ struct RqParams {
 unsigned query_resident_blocks();
 void launch_query(const DevScene& S, const RqParams& Q, bool any, bool count, unsigned blocks, hipStream_t stream);
 
+// Surface queries (rq_resolve, rt_query.hip): one thread per record turns a ray and its hit into
+// an rt_surface (four 16-B words) and, unless `materials` is null, an rt_surface_material (three),
+// by surface_eval (rt_surface.h).  S carries the shading streams (tri_nrm, inst, materials and,
+// for a textured scene, the texture tables); the tree is not read.
+struct RsParams {
+    const float4* rays;     // two words per record (rt_ray)
+    const float4* hits;     // two words per record (rt_ray_hit)
+    float4* surfaces;
+    float4* materials;      // or null
+    uint32_t n;
+};
+unsigned resolve_resident_blocks();
+void launch_resolve(const DevScene& S, const RsParams& P, unsigned blocks, hipStream_t stream);
+
 // Utility kernels (rt_util.hip)
 // G-buffer-guided denoise for RT_SCALER_DENOISED (rt_present.hip); returns tmp0 or tmp1, whichever
 // holds the result (passes = 0 returns the demodulated radiance unremodulated: callers pass >= 1)

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_kernels.h"
+#include "rt_surface.h"
 #include "rt_trav.h"
 #include "rt_wf_queue.h"   // lane_id, mbcnt64
 
@@ -105,7 +106,56 @@ rq_trace(DevScene S, RqParams Q) {
                          overflow);
 }
 
+// ---- surface queries: a ray and its hit record -> rt_surface (+ rt_surface_material) ---------------
+// One record per thread, grid-stride over at most the resident blocks.  Per record two 16-B loads
+// of the ray, two of the hit, the triangle's tri_nrm line (its fourth word only when the submesh
+// has a bound map), the instance matrix and the Material straight from global memory (KBs, cache
+// resident: staging them in LDS per block would cost small batches more than it saves), then four
+// 16-B stores, seven with materials.  No LDS, no atomics.  The record index stays 64-bit: n may
+// be anything below 2^32 and the last stride may step past it.
+template <bool MATERIAL, bool TEXTURED>
+__global__ void __launch_bounds__(kBlock) rq_resolve(DevScene S, RsParams P) {
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)P.n; i += stride) {
+        const float4 o4 = P.rays[2 * i], d4 = P.rays[2 * i + 1];
+        const float4 h0 = P.hits[2 * i];
+        const uint4 h1 = reinterpret_cast<const uint4*>(P.hits)[2 * i + 1];
+        SurfaceWords r;
+        surface_eval<MATERIAL, TEXTURED>(S, o4, d4, h0, h1, r);
+        float4* const so = P.surfaces + 4 * i;
+        so[0] = r.s0;
+        so[1] = r.s1;
+        so[2] = r.s2;
+        reinterpret_cast<uint4*>(so)[3] = r.s3;
+        if (MATERIAL) {
+            float4* const mo = P.materials + 3 * i;
+            mo[0] = r.m0;
+            mo[1] = r.m1;
+            mo[2] = r.m2;
+        }
+    }
+}
+
 }  // namespace
+
+unsigned resolve_resident_blocks() {
+    static const unsigned resident = [] {
+        int dev = 0, cus = 256, per = 0;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        // the variant that holds the most registers: one figure serves all four
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rq_resolve<true, true>, kBlock, 0) != hipSuccess || per < 1)
+            per = 4;
+        return (unsigned)(cus * per);
+    }();
+    return resident;
+}
+
+void launch_resolve(const DevScene& S, const RsParams& P, unsigned blocks, hipStream_t stream) {
+    const bool mat = P.materials != nullptr, tex = S.textured != 0;
+    auto kernel = mat ? (tex ? rq_resolve<true, true> : rq_resolve<true, false>)
+                      : (tex ? rq_resolve<false, true> : rq_resolve<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, S, P);
+}
 
 unsigned query_resident_blocks() {
     static const unsigned resident = [] {

@@ -1,0 +1,135 @@
+// rt_scene_host.h — a scene description as host arrays in the layouts the kernels read: what
+// rt_scene_upload copies to the device (rt_api_scene.cpp) and what the host debug hooks walk
+// (rt_debug_trace_host there, rt_debug_resolve_host in rt_surface_host.cpp), so both see the same
+// checks and the same tables.  Internal; header-only.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "rt_ctx.h"
+
+namespace rt {
+
+// What rt_scene_upload accepts; the scene's sizes on success.  c may be null (the debug hooks).
+inline rt_status validate_scene(rt_ctx* c, const rt_scene_desc* sd, int& max_sub, uint64_t& nv, uint64_t& nt) {
+    if (sd->mesh_count == 0) FAIL(c, RT_ERR_INVALID_ARG, "scene has no meshes");
+    if (sd->light_count == 0 || !sd->lights) FAIL(c, RT_ERR_INVALID_ARG, "scene has no lights");
+    if (sd->mesh_count >= (1u << 24)) FAIL(c, RT_ERR_UNSUPPORTED, "too many meshes");
+    max_sub = 1;
+    nv = nt = 0;
+    for (uint32_t m = 0; m < sd->mesh_count; ++m) {
+        const rt_mesh_desc& md = sd->meshes[m];
+        if (!md.positions || !md.normals) FAIL(c, RT_ERR_INVALID_ARG, "mesh without positions/normals");
+        if (md.submesh_count == 0 || !md.submeshes) FAIL(c, RT_ERR_INVALID_ARG, "mesh without submeshes");
+        if (md.submesh_count > 256) FAIL(c, RT_ERR_UNSUPPORTED, "more than 256 submeshes in a mesh");
+        if (md.joint_count && (!md.joint_indices || !md.joint_weights)) FAIL(c, RT_ERR_INVALID_ARG, "skinned mesh without joint streams");
+        max_sub = std::max(max_sub, (int)md.submesh_count);
+        nv += md.vertex_count;
+        for (uint32_t s = 0; s < md.submesh_count; ++s) {
+            const rt_submesh_desc& sm = md.submeshes[s];
+            if (sm.index_count % 3) FAIL(c, RT_ERR_INVALID_ARG, "index count not a multiple of 3");
+            if (sm.index_count && !sm.indices) FAIL(c, RT_ERR_INVALID_ARG, "null indices");
+            for (int k = 0; k < RT_TEXTURE_SLOTS; ++k)
+                if (k != 4 && (sm.material.textureFlags >> k & 1u) &&   // the AO slot is never sampled
+                    (sm.textures[k] < 0 || (uint32_t)sm.textures[k] >= sd->texture_count || !sd->textures))
+                    FAIL(c, RT_ERR_INVALID_ARG, "textured material without a valid texture for a flagged slot");
+            for (uint32_t i = 0; i < sm.index_count; ++i)
+                if (sm.indices[i] >= md.vertex_count) FAIL(c, RT_ERR_INVALID_ARG, "index out of range");
+            nt += sm.index_count / 3;
+        }
+    }
+    if (nt >= (1ull << 31) || nv >= (1ull << 32)) FAIL(c, RT_ERR_UNSUPPORTED, "scene too large");
+    uint64_t ntexels = 0;
+    for (uint32_t t = 0; t < sd->texture_count; ++t) {
+        const rt_texture_desc& td = sd->textures[t];
+        if (!td.rgba8 || td.width == 0 || td.height == 0) FAIL(c, RT_ERR_INVALID_ARG, "bad texture");
+        ntexels += (uint64_t)td.width * td.height;
+    }
+    if (ntexels >= (1ull << 32)) FAIL(c, RT_ERR_UNSUPPORTED, "texture pool above 2^32 texels");
+    return RT_OK;
+}
+
+// A scene description flattened mesh by mesh: positions and normals with every mesh's vertices
+// after the previous one's, triangles as (three vertex ids, mesh << 8 | submesh), 12 floats of
+// transform per mesh.  nrm may be null.
+inline void flatten_scene(const rt_scene_desc* sd, std::vector<float4>& pos, std::vector<float4>* nrm,
+                          std::vector<uint4>& tri_info, std::vector<float>& inst) {
+    pos.clear();
+    tri_info.clear();
+    if (nrm) nrm->clear();
+    inst.assign(12 * (size_t)sd->mesh_count, 0.0f);
+    for (uint32_t m = 0; m < sd->mesh_count; ++m) {
+        const rt_mesh_desc& md = sd->meshes[m];
+        const uint32_t vbase = (uint32_t)pos.size();
+        std::memcpy(&inst[12 * (size_t)m], &md.transform, 48);
+        for (uint32_t v = 0; v < md.vertex_count; ++v) {
+            const rt_float3& p = md.positions[v];
+            pos.push_back(make_float4(p.x, p.y, p.z, 0.0f));
+            if (nrm) nrm->push_back(make_float4(md.normals[v].x, md.normals[v].y, md.normals[v].z, 0.0f));
+        }
+        for (uint32_t s = 0; s < md.submesh_count; ++s) {
+            const rt_submesh_desc& sm = md.submeshes[s];
+            for (uint32_t k = 0; k < sm.index_count / 3; ++k)
+                tri_info.push_back(make_uint4(vbase + sm.indices[3 * k + 0], vbase + sm.indices[3 * k + 1],
+                                              vbase + sm.indices[3 * k + 2], (m << 8) | s));
+        }
+    }
+}
+
+// Texture path: the texel pool, its table, every material slot's texture
+// ids and the per-vertex UVs (Model.vertexDescriptor's zero default when a mesh has none,
+// Model.swift:329-333).  Only mat_tex and `textured` are filled in for an untextured scene.
+struct TexTables {
+    bool textured = false;
+    std::vector<int4> mat_tex;      // DevScene::mat_tex
+    std::vector<uint4> info;        // DevScene::tex_info
+    std::vector<uint8_t> texels;    // DevScene::tex_texels
+    std::vector<float2> uv;         // DevScene::uv
+    float lut[512];                 // DevScene::tex_lut
+};
+inline void build_tex_tables(const rt_scene_desc* sd, int max_sub, uint32_t num_verts, TexTables& T) {
+    const uint32_t slots = (uint32_t)max_sub * sd->mesh_count;
+    T.mat_tex.assign(2 * (size_t)slots, make_int4(0, -1, -1, -1));
+    T.textured = false;
+    for (uint32_t m = 0; m < sd->mesh_count; ++m)
+        for (uint32_t s = 0; s < sd->meshes[m].submesh_count; ++s) {
+            const rt_submesh_desc& sm = sd->meshes[m].submeshes[s];
+            uint32_t flags = sm.material.textureFlags & ~(1u << 4);   // ENABLE_AO = 0
+            if (!flags) continue;
+            T.textured = true;
+            int t[8];
+            for (int k = 0; k < 8; ++k) t[k] = (k < RT_TEXTURE_SLOTS && (flags >> k & 1u)) ? sm.textures[k] : -1;
+            const size_t slot = (size_t)m * max_sub + s;
+            T.mat_tex[2 * slot] = make_int4((int)flags, t[0], t[1], t[2]);
+            T.mat_tex[2 * slot + 1] = make_int4(t[3], t[4], t[5], t[6]);
+        }
+    if (!T.textured) return;
+    T.info.resize(sd->texture_count);
+    uint64_t off = 0;
+    for (uint32_t t = 0; t < sd->texture_count; ++t) {
+        const rt_texture_desc& td = sd->textures[t];
+        T.info[t] = make_uint4((uint32_t)off, td.width, td.height, 0u);
+        off += (uint64_t)td.width * td.height;
+    }
+    T.texels.resize(off * 4);
+    for (uint32_t t = 0; t < sd->texture_count; ++t)
+        std::memcpy(&T.texels[4 * (size_t)T.info[t].x], sd->textures[t].rgba8, 4 * (size_t)T.info[t].y * T.info[t].z);
+    T.uv.assign(num_verts, make_float2(0.0f, 0.0f));
+    uint32_t vbase = 0;
+    for (uint32_t m = 0; m < sd->mesh_count; ++m) {
+        const rt_mesh_desc& md = sd->meshes[m];
+        if (md.uvs)
+            for (uint32_t v = 0; v < md.vertex_count; ++v) T.uv[vbase + v] = make_float2(md.uvs[v].x, md.uvs[v].y);
+        vbase += md.vertex_count;
+    }
+    // texel byte -> float: [0, 256) linear b / 255, [256, 512) sRGB EOTF (MTKTextureLoader .SRGB)
+    for (int b = 0; b < 256; ++b) {
+        const double v = b / 255.0;
+        T.lut[b] = (float)v;
+        T.lut[256 + b] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4));
+    }
+}
+
+}  // namespace rt

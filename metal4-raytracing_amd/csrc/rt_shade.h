@@ -109,7 +109,7 @@ __device__ __forceinline__ f3 ldf3(const rt_float3& v) { return mk3(v.x, v.y, v.
 // kernel, i.e. bilinear from LOD 0 (Raytracing.metal:420).  Here: texel centres at integer + 0.5,
 // wrap-around neighbours, each corner decoded through the byte table (sRGB for base color and
 // emission maps, linear otherwise; alpha always linear), weights applied in a fixed order.
-__device__ __forceinline__ float4 tex_sample(const DevScene& S, int t, f2 uv, bool srgb) {
+__host__ __device__ __forceinline__ float4 tex_sample(const DevScene& S, int t, f2 uv, bool srgb) {
     const uint4 ti = S.tex_info[t];
     const int w = (int)ti.y, h = (int)ti.z;
     float x = uv.x * (float)w - 0.5f, y = uv.y * (float)h - 0.5f;
@@ -133,11 +133,11 @@ __device__ __forceinline__ float4 tex_sample(const DevScene& S, int t, f2 uv, bo
                        bil(Lc, c00.z, c10.z, c01.z, c11.z), bil(L, c00.w, c10.w, c01.w, c11.w));
 }
 
-__device__ __forceinline__ f2 ld2(const float2& v) { return f2{v.x, v.y}; }
+__host__ __device__ __forceinline__ f2 ld2(const float2& v) { return f2{v.x, v.y}; }
 
 // computeTangentBasis (Raytracing.metal:185-218): object-space dP/du, dP/dv of the hit triangle
 // from its vertices in the order (indices[3t+1], indices[3t+2], indices[3t]).
-__device__ __forceinline__ bool tangent_basis(const DevScene& S, const uint4& ti, f3& tangent, f3& bitangent) {
+__host__ __device__ __forceinline__ bool tangent_basis(const DevScene& S, const uint4& ti, f3& tangent, f3& bitangent) {
     const f3 p0 = ld3(S.pos[ti.y]), p1 = ld3(S.pos[ti.z]), p2 = ld3(S.pos[ti.x]);
     const f2 uv0 = ld2(S.uv[ti.y]), uv1 = ld2(S.uv[ti.z]), uv2 = ld2(S.uv[ti.x]);
     const f3 e1 = p1 - p0, e2 = p2 - p0;

@@ -12,7 +12,14 @@ Each is the median of five runs after two warm-up runs, in a child process of it
 every run has a time limit (the child is killed when a run does not report in time).  After the
 timed runs each child does one counting run for the node visits and triangle tests per ray.
 
-    python tools/query_bench.py [--scene c3g] [--width 1920] [--height 1080] [--run-timeout 60]
+--resolve runs one other leg instead and prints its own JSON line:
+(c) resolve: Renderer.resolve on the rays and hit records of (b), with and without material
+    records, each timed by HIP events around the launch on its stream (median of five after two
+    warm-up runs).  Reported as records per second (Ghits/s; the share of records that are hits
+    beside it) and as the fraction of the HBM floor: 64 B of ray and hit in, the 64-B tri_nrm line
+    and 64 B (112 B with materials) out per record, at 6.3 TB/s.
+
+    python tools/query_bench.py [--resolve] [--scene c3g] [--width 1920] [--height 1080] [--run-timeout 60]
 """
 import argparse
 import importlib
@@ -113,6 +120,38 @@ def child_query(args):
     return 0
 
 
+HBM_BYTES_PER_S = 6.3e12   # achievable HBM bandwidth the floor of leg (c) is stated against
+RESOLVE_BYTES = {"surface": 64 + 64 + 64, "surface_material": 64 + 64 + 112}   # compulsory bytes per record
+
+
+def child_resolve(args):
+    rt = _rt()
+    import torch
+    W, H = args.width, args.height
+    R = rt.Renderer(rt.Scene.preset(args.scene), 64, 64)
+    dev = torch.device("cuda", 0)
+    rays = camera_rays(rt, W, H, dev)
+    n = rays.shape[0]
+    hits = R.trace(rays)
+    R.wait()
+    surf = torch.empty((n, 16), dtype=torch.float32, device=dev)
+    mat = torch.empty((n, 12), dtype=torch.float32, device=dev)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.synchronize()
+    nhit = int((hits.triangle != -1).sum().item())
+    _emit(ready=True)
+    for kind, material in (("surface", False), ("surface_material", True)):
+        for k in range(WARMUP + RUNS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            R.resolve(rays, hits, material=material, out=(surf, mat) if material else surf, stream=stream.cuda_stream)
+            e1.record(stream)
+            e1.synchronize()
+            _emit(run=k, kind=kind, records=n, hits=nhit, ms=float(e0.elapsed_time(e1)))
+    R.close()
+    return 0
+
+
 def run_child(kind, args):
     """The child's reports; every line has to arrive within its time limit."""
     cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--scene", args.scene, "--width", str(args.width),
@@ -160,11 +199,31 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--run-timeout", type=float, default=60.0, help="seconds each run may take")
     ap.add_argument("--setup-timeout", type=float, default=240.0, help="seconds the scene load and BVH build may take")
-    ap.add_argument("--child", choices=["frame", "query"])
+    ap.add_argument("--resolve", action="store_true", help="leg (c) only: the surface query on leg (b)'s hits")
+    ap.add_argument("--child", choices=["frame", "query", "resolve"])
     args = ap.parse_args()
     if args.child:
-        return (child_frame if args.child == "frame" else child_query)(args)
+        return {"frame": child_frame, "query": child_query, "resolve": child_resolve}[args.child](args)
     res = {"scene": args.scene, "width": args.width, "height": args.height, "rays": args.width * args.height * 4}
+    if args.resolve:
+        lines, err = run_child("resolve", args)
+        for kind, nbytes in RESOLVE_BYTES.items():
+            runs = [r for r in lines if r.get("kind") == kind and r["run"] >= WARMUP]
+            if not err and len(runs) != RUNS:
+                err = f"resolve ({kind}): {len(runs)} timed runs reported, not {RUNS}"
+            if err:
+                res["error"] = err
+                print(json.dumps(res))
+                return 1
+            rates = [r["records"] / r["ms"] * 1e-6 for r in runs]   # records / ms -> Ghits/s
+            res[f"{kind}_ghits"] = statistics.median(rates)
+            res[f"{kind}_runs_ghits"] = [round(x, 4) for x in rates]
+            res[f"{kind}_ms"] = statistics.median(r["ms"] for r in runs)
+            res[f"{kind}_floor_ghits"] = round(HBM_BYTES_PER_S / nbytes * 1e-9, 2)
+            res[f"{kind}_floor_fraction"] = round(res[f"{kind}_ghits"] * 1e9 * nbytes / HBM_BYTES_PER_S, 4)
+            res["hit_share"] = round(runs[-1]["hits"] / runs[-1]["records"], 4)
+        print(json.dumps(res))
+        return 0
     for kind in ("frame", "query"):
         t0 = time.time()
         lines, err = run_child(kind, args)
