@@ -25,6 +25,8 @@
  *                              raytracingKernel + ping-pong swap (Renderer.swift:1405-1503)
  *   rt_trace_closest/rt_trace_any  `intersector.intersect` called from any other kernel: batches
  *                              of the caller's rays against the built scene
+ *   rt_resolve_hits / rt_shade_hits  what such a kernel does with the hit: the Resource-buffer
+ *                              reads (:324-456) and the shading up to the next ray (:517-774)
  *   rt_read_radiance/rt_read_aux  (no reference equivalent: the reference never reads back;
  *                              replaces presenting dstTex/depthTex/motionTex to MetalFX)
  *
@@ -514,6 +516,89 @@ rt_status rt_resolve_hits(rt_ctx* ctx, const rt_ray* rays, const rt_ray_hit* hit
 rt_status rt_resolve_hits_on(rt_ctx* ctx, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
                              rt_surface_material* materials, void* hip_stream);
 
+/* ---- Shading queries: a resolved hit and its path state turned into the path's next rays -------
+ * Everything raytracingKernel does between the material fetch and the next `intersect`
+ * (Raytracing.metal:517-774): the glass branch (Fresnel choice, reflect / refract, transparency
+ * passes), the light pick and the four light types, the GGX / legacy direct term with its shadow
+ * ray, the cosine-hemisphere bounce, the throughput and the bounce / step bookkeeping, each drawing
+ * from the renderer's own Halton dimension.  With the queries above the loop closes:
+ *   trace -> resolve -> shade -> trace_any (shadow rays) + trace (next rays) -> resolve -> shade ...
+ * and a caller runs the renderer's path tracer one bounce at a time: a frame re-assembled this way
+ * (pixel = the sum of its samples' radiance in sample order / samples) equals rt_render_frame's
+ * radiance of frame 0 bit for bit.
+ *
+ * One record per path, all DEVICE pointers, every record read and written as whole 16-B words. */
+typedef struct rt_path {          /* 48 B, three 16-B words, 16-byte aligned */
+    float    throughput[3];       /* the renderer's `color`; (1,1,1) at the camera */
+    uint32_t sample;              /* the path's Halton index: random offset + frameIndex * stride + sample */
+    float    radiance[3];         /* the renderer's `accum` */
+    uint32_t flags;               /* RT_PATH_* */
+    int32_t  bounce, step, transparency_passes;
+    uint32_t reserved;            /* 0 */
+} rt_path;
+#define RT_PATH_ALIVE  1u   /* in: shade this record; out: trace next_rays[i] again */
+#define RT_PATH_SHADOW 2u   /* out: shadow_rays[i] / contrib[i] are live for this step */
+RT_STATIC_ASSERT(sizeof(rt_path) == 48, "rt_path is three 16-B words");
+
+typedef struct rt_shade_opts {    /* 32 B */
+    int32_t shading_mode;         /* ShadingMode* of Uniforms */
+    int32_t max_bounces;          /* 1 .. 12, as rt_render_frame accepts */
+    int32_t light_count;          /* Uniforms.lightCount; 0 = every uploaded light */
+    int32_t reserved[5];
+} rt_shade_opts;
+RT_STATIC_ASSERT(sizeof(rt_shade_opts) == 32, "rt_shade_opts is 32 B");
+
+/* Semantics:
+ *  - Inputs, per record: the ray that was traced (only its direction is read), its rt_surface and
+ *    rt_surface_material from rt_resolve_hits (the material record is required here) and the path
+ *    state.  `randoms` may be NULL.
+ *  - Outputs: the path is updated in place (throughput, radiance with this hit's emission added,
+ *    bounce / step / transparency_passes, flags).  next_rays[i] is the ray to trace next, tmax =
+ *    INFINITY.  shadow_rays[i] is the light connection, tmax = lightDistance - 1e-3 (INFINITY for
+ *    a sun light).  contrib[i] is (r, g, b, 0), four floats per record.
+ *  - Bit-exactness: every float is the one the renderer's shading forms at that hit with the same
+ *    path state: the PBR and the legacy mode, all four light types, glass, normal-mapped shading
+ *    normals (already in the surface record).
+ *  - Applying the shadow ray is the caller's, as the renderer does it: rt_trace_any on the flagged
+ *    shadow rays, then radiance += contrib where not occluded.  The emission of this step is
+ *    already in `radiance` (the renderer's order).
+ *  - Record rules.  RT_PATH_SHADOW is an output: every call sets or clears it.
+ *      ALIVE clear on input: the path is untouched but for SHADOW, which is cleared; the three
+ *      output records are zero-filled with tmax = -1 on both rays.
+ *      ALIVE set with bounce >= max_bounces, or with a miss surface (triangle == RT_MISS): ALIVE
+ *      (and SHADOW) are cleared and nothing else changes (the renderer's `while` / `break`); the
+ *      outputs are zero-filled as above.
+ *      A step without a shadow ray: SHADOW is clear, shadow ray and contrib zero-filled, tmax = -1.
+ *      A step that ends the path (throughput cut-off, last bounce): ALIVE is clear and the next
+ *      ray is zero-filled with tmax = -1.
+ *      Callers trace only flagged records; what the traversal does with a zero direction is not
+ *      part of the interface.
+ *  - randoms == NULL uses the renderer's Halton numbers at index paths[i].sample, dimensions
+ *      light pick 2 + 6 step; area-light u, v 2 + 6 step + 1, + 2; glass choice 2 + 6 step + 5;
+ *      hemisphere r0, r1 2 + 5 step + 3, 2 + 5 step + 4 (the reference's own 5-stride, :763-764).
+ *    A dimension above the table's last (1023; the renderer's states stay below 944) reads the
+ *    last.  Otherwise `randoms` holds n x 8 floats, two 16-B words per record:
+ *    (light, area_u, area_v, glass_choice), (r0, r1, 0, 0), used in their place.
+ *  - The light index is min((int)(x * count), count - 1) clamped to [0, count - 1], NaN -> 0: the
+ *    renderer's index for every Halton value, and never one outside the lights for a caller's.
+ *  - Not part of it: debug texture modes, the G-buffer, depth / motion, extra samples, the EMA.
+ *  - The lights are the uploaded scene's (rt_scene_upload waits for pending queries first).  An
+ *    effective light count of 0, or one above the uploaded count, is RT_ERR_INVALID_ARG.
+ *  - Ordering against updates, streams, slots, rt_wait and rt_destroy: exactly as for
+ *    rt_resolve_hits.  Not folded into rt_query_stats.  Frames rendered with shade queries
+ *    interleaved are bit-identical to frames rendered without.  Needs the scene only (no BVH).
+ *  - Errors: NULL opts, or any pointer but `randoms` NULL with n > 0: RT_ERR_INVALID_ARG.  Any
+ *    pointer not 16-byte aligned, or an opts field out of range: RT_ERR_INVALID_ARG.  Before
+ *    rt_scene_upload: RT_ERR_STATE.  n == 0: RT_OK, nothing is launched.
+ *  - Aliasing: `paths` is updated in place; next_rays may alias rays (each record is read before
+ *    it is written, by one thread).  No other two arrays may overlap. */
+rt_status rt_shade_hits(rt_ctx* ctx, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                        const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths,
+                        rt_ray* next_rays, rt_ray* shadow_rays, float* contrib);
+rt_status rt_shade_hits_on(rt_ctx* ctx, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                           const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths,
+                           rt_ray* next_rays, rt_ray* shadow_rays, float* contrib, void* hip_stream);
+
 /* Library build identification (kernel code object arch etc). */
 const char* rt_version(void);
 
@@ -532,6 +617,13 @@ rt_status rt_debug_trace_host(const rt_scene_desc* scene, const float* rays, con
  * base-colour maps included. */
 rt_status rt_debug_resolve_host(const rt_scene_desc* scene, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n,
                                 rt_surface* surfaces, rt_surface_material* materials);
+
+/* Test hook (host only, no device): rt_shade_hits over host arrays and the given lights, by the
+ * code the kernel runs, compiled for the host.  All pointers are HOST pointers; the same checks
+ * (light_count here is the number of lights given; opts->light_count 0 = all of them). */
+rt_status rt_debug_shade_host(const Light* lights, uint32_t light_count, const rt_shade_opts* opts, const rt_ray* rays,
+                              const rt_surface* surfaces, const rt_surface_material* materials, const float* randoms,
+                              uint32_t n, rt_path* paths, rt_ray* next_rays, rt_ray* shadow_rays, float* contrib);
 
 #ifdef __cplusplus
 }

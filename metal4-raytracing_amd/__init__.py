@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (TEXTURE_SLOTS, Tuning, Camera, Float3, Light, MaterialOverride, PackedFloat4x3, SceneDesc, Stats, TextureDesc,
-                   TileSet, Uniforms, Ray, RayHit, QueryStats,
+                   TileSet, Uniforms, Ray, RayHit, QueryStats, Path, ShadeOpts,
                    f3)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -140,6 +140,37 @@ def debug_resolve_host(scene, rays, hits, material=True):
     _check(lib().rt_debug_resolve_host(C.byref(d_), r.ctypes.data, h.ctypes.data, n, surf.ctypes.data,
                                        mat.ctypes.data if material else None))
     return Surface(surf, surf.view(np.int32), mat, mat.view(np.int32) if material else None)
+
+
+def debug_shade_host(lights, rays, surface, paths, randoms=None, shading_mode=0, max_bounces=2, light_count=0):
+    """Test hook: rt_shade_hits on the host (rt_debug_shade_host) with the given lights (a list of
+    Light, or a Scene: its lights).  rays: (n, 8) float32; surface: a Surface with materials (numpy);
+    paths: a Paths object or its (n, 12) float32 buffer, NOT modified: the updated copy is
+    returned; randoms: None or (n, 8) float32.  Returns a Shaded of numpy arrays."""
+    if isinstance(lights, Scene):
+        d = lights.desc()
+        lights = [d.lights[k] for k in range(d.light_count)]
+    arr = (Light * max(len(lights), 1))(*lights)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    n = r.shape[0]
+    if surface.material_buffer is None:
+        raise ValueError("shade needs the material records (resolve with material=True)")
+    s = np.ascontiguousarray(surface.buffer, np.float32)
+    m = np.ascontiguousarray(surface.material_buffer, np.float32)
+    pb = paths.buffer if isinstance(paths, Paths) else paths
+    if not isinstance(pb, np.ndarray) or pb.dtype != np.float32:
+        raise ValueError("paths must be float32 (n, 12) rt_path records")
+    p = np.array(pb, np.float32, copy=True, order="C")
+    rnd = None if randoms is None else np.ascontiguousarray(randoms, np.float32)
+    for name, x, cols in (("surface", s, 16), ("materials", m, 12), ("paths", p, 12), ("randoms", rnd, 8)):
+        if x is not None and x.shape != (n, cols):
+            raise ValueError(f"{name} must be ({n}, {cols}), not {x.shape}")
+    nxt, sh, con = np.empty((n, 8), np.float32), np.empty((n, 8), np.float32), np.empty((n, 4), np.float32)
+    o = _shade_opts(shading_mode, max_bounces, light_count)
+    _check(lib().rt_debug_shade_host(arr, len(lights), C.byref(o), r.ctypes.data, s.ctypes.data, m.ctypes.data,
+                                     rnd.ctypes.data if rnd is not None else None, n, p.ctypes.data, nxt.ctypes.data,
+                                     sh.ctypes.data, con.ctypes.data))
+    return Shaded(Paths(p, p.view(np.int32)), nxt, sh, con)
 
 
 def glass_override():
@@ -353,6 +384,50 @@ class Surface:
 
     def __len__(self):
         return self.buffer.shape[0]
+
+
+class Paths:
+    """Path states of Renderer.shade: `buffer` holds the (n, 12) rt_path records and the fields are
+    views of it.  float32: throughput (n, 3), radiance (n, 3).  int32: sample (the Halton index),
+    flags (ALIVE / SHADOW bits), bounce, step, transparency_passes.  Torch tensors on the device
+    path, numpy arrays on the host path."""
+
+    ALIVE, SHADOW = _abi.RT_PATH_ALIVE, _abi.RT_PATH_SHADOW
+
+    def __init__(self, buffer, as_int):
+        self.buffer = buffer
+        self.throughput, self.radiance = buffer[:, 0:3], buffer[:, 4:7]
+        self.sample, self.flags = as_int[:, 3], as_int[:, 7]
+        self.bounce, self.step, self.transparency_passes = as_int[:, 8], as_int[:, 9], as_int[:, 10]
+
+    def __len__(self):
+        return self.buffer.shape[0]
+
+    @property
+    def alive(self):
+        return (self.flags & self.ALIVE) != 0
+
+    @property
+    def shadow(self):
+        return (self.flags & self.SHADOW) != 0
+
+
+class Shaded:
+    """Results of Renderer.shade: `paths` (the Paths given, updated in place), `next_rays` and
+    `shadow_rays` ((n, 8) rt_ray records, to trace where paths.alive / paths.shadow) and `contrib`
+    ((n, 4): r, g, b, 0; add to paths.radiance where the shadow ray is not occluded)."""
+
+    def __init__(self, paths, next_rays, shadow_rays, contrib):
+        self.paths, self.next_rays, self.shadow_rays, self.contrib = paths, next_rays, shadow_rays, contrib
+
+    def __len__(self):
+        return len(self.paths)
+
+
+def _shade_opts(shading_mode, max_bounces, light_count):
+    o = _abi.ShadeOpts()
+    o.shading_mode, o.max_bounces, o.light_count = int(shading_mode), int(max_bounces), int(light_count)
+    return o
 
 
 class Renderer:
@@ -580,6 +655,107 @@ class Renderer:
             s, m = surf.cpu().numpy(), mat.cpu().numpy() if material else None
             return Surface(s, s.view(np.int32), m, m.view(np.int32) if material else None)
         return Surface(surf, surf.view(torch.int32), mat, mat.view(torch.int32) if material else None)
+
+    @staticmethod
+    def make_paths(sample_indices):
+        """(n, 12) rt_path records at the camera as a Paths: ALIVE, throughput 1, everything else 0,
+        `sample` = the given Halton indices (random offset + frameIndex * stride + sample).  A
+        torch tensor on their device when they are a tensor, a numpy array otherwise."""
+        try:
+            import torch
+            on_torch = isinstance(sample_indices, torch.Tensor)
+        except ImportError:
+            on_torch = False
+        if on_torch:
+            idx = sample_indices.reshape(-1).to(torch.int64)
+            p = torch.zeros((idx.shape[0], 12), dtype=torch.float32, device=idx.device)
+            pi = p.view(torch.int32)
+            p[:, 0:3] = 1.0
+            pi[:, 3] = ((idx + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)   # the uint32's bits
+            pi[:, 7] = _abi.RT_PATH_ALIVE
+            return Paths(p, pi)
+        idx = np.asarray(sample_indices).reshape(-1).astype(np.int64)
+        p = np.zeros((idx.shape[0], 12), np.float32)
+        pu = p.view(np.uint32)
+        p[:, 0:3] = 1.0
+        pu[:, 3] = idx.astype(np.uint32)
+        pu[:, 7] = _abi.RT_PATH_ALIVE
+        return Paths(p, p.view(np.int32))
+
+    def shade(self, rays, surface, paths, randoms=None, shading_mode=None, max_bounces=None, light_count=None, out=None,
+              stream=None):
+        """rt_shade_hits: what the renderer does between a resolved hit and the next ray.  `rays`
+        are the (n, 8) rays that were traced, `surface` their Surface from resolve (with
+        materials), `paths` a Paths (make_paths) or its (n, 12) buffer.  Returns a Shaded: the
+        paths updated, next_rays to trace where paths.alive, shadow_rays to trace_any where
+        paths.shadow, contrib to add to paths.radiance where those are not occluded.
+        shading_mode, max_bounces and light_count default to the Renderer's current uniforms;
+        randoms: None = the renderer's Halton numbers, or (n, 8) float32 (light, area u, area v,
+        glass choice, r0, r1, 0, 0).
+
+        Device path (`rays` is a torch tensor; so are the others): `paths` is updated IN PLACE,
+        enqueued on `stream` (as in trace) without a host wait; `out` is a triple of float32
+        tensors (next_rays (n, 8), shadow_rays (n, 8), contrib (n, 4)); next_rays may be `rays`.
+        Host path (`rays` is a host array): staged through torch, waited for, returned as numpy;
+        the given paths are not modified."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = not isinstance(rays, torch.Tensor)
+        pb = paths.buffer if isinstance(paths, Paths) else paths
+        sb, mb = surface.buffer, surface.material_buffer
+        if mb is None:
+            raise ValueError("shade needs the material records (resolve with material=True)")
+        named = [("rays", rays, 8), ("surface", sb, 16), ("materials", mb, 12), ("paths", pb, 12)]
+        if randoms is not None:
+            named.append(("randoms", randoms, 8))
+        if host:
+            staged = []
+            for name, x, cols in named:
+                if isinstance(x, torch.Tensor):
+                    raise ValueError(f"rays on the host but {name} on the device")
+                x = np.ascontiguousarray(x)
+                if x.dtype != np.float32 or x.ndim != 2 or x.shape[1] != cols:
+                    raise ValueError(f"{name} must be float32 (n, {cols}) records")
+                staged.append(torch.from_numpy(x).to(dev))
+        else:
+            staged = [x for _, x, _ in named]
+            for name, x, cols in named:
+                if (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != cols
+                        or not x.is_contiguous() or x.device != dev):
+                    raise ValueError(f"{name} must be a contiguous float32 (n, {cols}) tensor on {dev}")
+        n = staged[0].shape[0]
+        for (name, _, _), x in zip(named, staged):
+            if x.shape[0] != n:
+                raise ValueError(f"{n} rays but {x.shape[0]} {name} records")
+        r, s, m, p = staged[:4]
+        rnd = staged[4] if randoms is not None else None
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
+            raise ValueError("out must be (next_rays, shadow_rays, contrib)")
+        outs = []
+        for k, (name, cols) in enumerate((("next_rays", 8), ("shadow_rays", 8), ("contrib", 4))):
+            x = out[k] if out is not None else torch.empty((n, cols), dtype=torch.float32, device=dev)
+            if (not isinstance(x, torch.Tensor) or tuple(x.shape) != (n, cols) or x.dtype != torch.float32
+                    or not x.is_contiguous() or x.device != dev):
+                raise ValueError(f"out {name} must be a contiguous float32 ({n}, {cols}) tensor on {dev}")
+            outs.append(x)
+        o = _shade_opts(self.shadingMode if shading_mode is None else shading_mode,
+                        self.maxBounces if max_bounces is None else max_bounces,
+                        self.light_count if light_count is None else light_count)
+        if host:
+            torch.cuda.current_stream(dev).synchronize()   # the staging copies and the allocator's stream
+        vp = C.c_void_p
+        args = (self._ctx, C.byref(o), vp(r.data_ptr()), vp(s.data_ptr()), vp(m.data_ptr()),
+                vp(rnd.data_ptr()) if rnd is not None else None, n, vp(p.data_ptr()), vp(outs[0].data_ptr()),
+                vp(outs[1].data_ptr()), vp(outs[2].data_ptr()))
+        if stream is None:
+            _check(lib().rt_shade_hits(*args), self._ctx)
+        else:
+            _check(lib().rt_shade_hits_on(*args, vp(stream)), self._ctx)
+        if host:
+            self.wait()
+            pn = p.cpu().numpy()
+            return Shaded(Paths(pn, pn.view(np.int32)), *(x.cpu().numpy() for x in outs))
+        return Shaded(paths if isinstance(paths, Paths) else Paths(p, p.view(torch.int32)), *outs)
 
     def query_stats(self):
         """rt_get_query_stats (waits for pending queries): the last query and the running totals."""

@@ -222,6 +222,19 @@ class SurfaceMaterial(C.Structure):  # rt_surface_material: 48 B, three 16-B wor
 RT_SURFACE_HAS_UV, RT_SURFACE_BACKFACE, RT_SURFACE_NORMAL_MAPPED, RT_SURFACE_TRANSMISSIVE = 1, 2, 4, 8
 
 
+class Path(C.Structure):  # rt_path: 48 B, three 16-B words
+    _fields_ = [("throughput", C.c_float * 3), ("sample", C.c_uint32), ("radiance", C.c_float * 3), ("flags", C.c_uint32),
+                ("bounce", C.c_int32), ("step", C.c_int32), ("transparency_passes", C.c_int32), ("reserved", C.c_uint32)]
+
+
+RT_PATH_ALIVE, RT_PATH_SHADOW = 1, 2
+
+
+class ShadeOpts(C.Structure):  # rt_shade_opts: 32 B
+    _fields_ = [("shading_mode", C.c_int32), ("max_bounces", C.c_int32), ("light_count", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
 class QueryStats(C.Structure):  # rt_query_stats
     _fields_ = [
         ("rays", C.c_uint64),
@@ -287,8 +300,8 @@ EXPORTED_SYMBOLS = [
     "rt_pack_tiles_host", "rt_unpack_tiles_host",
     "rt_set_counting", "rt_set_device_spans", "rt_set_graphs", "rt_get_stats", "rt_set_tuning", "rt_get_tuning",
     "rt_trace_closest", "rt_trace_any", "rt_trace_closest_on", "rt_trace_any_on", "rt_get_query_stats",
-    "rt_resolve_hits", "rt_resolve_hits_on",
-    "rt_version", "rt_debug_trace_host", "rt_debug_resolve_host",
+    "rt_resolve_hits", "rt_resolve_hits_on", "rt_shade_hits", "rt_shade_hits_on",
+    "rt_version", "rt_debug_trace_host", "rt_debug_resolve_host", "rt_debug_shade_host",
     # rt_scene.h
     "rt_material_override_glass", "rt_scene_new", "rt_scene_free", "rt_scene_last_error",
     "rt_scene_add_obj", "rt_scene_add_usd", "rt_scene_add_procedural", "rt_scene_set_lights", "rt_scene_set_light_intensity",
@@ -347,6 +360,9 @@ def declare(lib):
         "rt_resolve_hits": (st, [vp, vp, vp, C.c_uint32, vp, vp]),
         "rt_resolve_hits_on": (st, [vp, vp, vp, C.c_uint32, vp, vp, vp]),
         "rt_debug_resolve_host": (st, [P(SceneDesc), vp, vp, C.c_uint32, vp, vp]),
+        "rt_shade_hits": (st, [vp, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+        "rt_shade_hits_on": (st, [vp, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
+        "rt_debug_shade_host": (st, [P(Light), C.c_uint32, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
         "rt_version": (C.c_char_p, []),
         "rt_debug_trace_host": (st, [P(SceneDesc), P(C.c_float), P(C.c_float), C.c_uint32, C.c_int32, P(C.c_float),
                                      P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32)]),

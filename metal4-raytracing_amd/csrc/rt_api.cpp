@@ -22,26 +22,8 @@ constexpr int kMaxTuneShadeBlocks = 65536;
 constexpr int kRefitRebuildPctDefault = 150;
 
 std::vector<HaltonDim> halton_table() {
-    std::vector<HaltonDim> t;
-    uint32_t n = 2;
-    while ((int)t.size() < RT_HALTON_DIMS) {
-        bool prime = true;
-        for (auto& h : t) {
-            if (h.b * h.b > n) break;
-            if (n % h.b == 0) { prime = false; break; }
-        }
-        if (prime) {
-            HaltonDim h;
-            h.b = n;
-            uint32_t l = 0;
-            while ((1u << l) < n) ++l;              // 2^(l-1) < b <= 2^l
-            h.m = (uint32_t)(((1ull << (31 + l)) + n - 1) / n);
-            h.sh = l - 1;
-            h.invB = 1.0f / (float)n;
-            t.push_back(h);
-        }
-        ++n;
-    }
+    std::vector<HaltonDim> t(RT_HALTON_DIMS);
+    halton_table_fill(t.data(), RT_HALTON_DIMS);
     return t;
 }
 

@@ -3,12 +3,13 @@
 // frame would read, and rt_get_query_stats reports them.  The replacement of Metal's
 // `intersector.intersect` called outside raytracingKernel.  rt_resolve_hits enqueues one
 // rq_resolve launch that turns rays and their hit records into surface and material records, by
-// the same generation rule.  Queries share nothing writable with frames: their counters, events
+// the same generation rule, and rt_shade_hits one rq_shade launch that turns those records and the
+// path states into the paths' next rays (lights and Halton table only).  Queries share nothing writable with frames: their counters, events
 // and statistics are their own (QuerySlot, rt_ctx.h).
 #include <algorithm>
 #include <cstring>
 
-#include "rt_ctx.h"
+#include "rt_scene_host.h"
 
 using namespace rt;
 
@@ -179,6 +180,40 @@ rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_
     HIPC(c, hipGetLastError());
     return commit_query(c, *qp, stream, true);
 }
+
+rt_status shade(rt_ctx* c, const rt_shade_opts* o, const rt_ray* rays, const rt_surface* surfaces,
+                const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths, rt_ray* next_rays,
+                rt_ray* shadow_rays, float* contrib, hipStream_t stream, bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (rt_status st = validate_shade(c, o, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib))
+        return st;
+    if (!c->scene_ready) FAIL(c, RT_ERR_STATE, "shading query before rt_scene_upload");
+    int lights = 0;
+    if (rt_status st = shade_light_count(c, o, (uint32_t)c->h_lights.size(), lights)) return st;
+    if (n == 0) return RT_OK;
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;   // the shading reads no geometry: lights and the Halton table only
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    ShParams P;
+    P.rays = (const float4*)rays;
+    P.surfaces = (const float4*)surfaces;
+    P.materials = (const float4*)materials;
+    P.randoms = (const float4*)randoms;
+    P.paths = (float4*)paths;
+    P.next_rays = (float4*)next_rays;
+    P.shadow_rays = (float4*)shadow_rays;
+    P.contrib = (float4*)contrib;
+    P.lights = (const Light*)c->d_lights.p;
+    P.halton = (const HaltonDim*)c->d_halton.p;
+    P.n = n;
+    P.shading_mode = o->shading_mode;
+    P.max_bounces = o->max_bounces;
+    P.light_count = lights;
+    const unsigned blocks = std::min(shade_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u);
+    launch_shade(P, blocks, stream);
+    HIPC(c, hipGetLastError());
+    return commit_query(c, *qp, stream, true);   // as a resolve: `done` only, nothing folded
+}
 }  // namespace
 
 rt_status drain_queries(rt_ctx* c) {
@@ -213,6 +248,19 @@ rt_status rt_resolve_hits(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits,
 rt_status rt_resolve_hits_on(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
                              rt_surface_material* materials, void* stream) {
     return resolve(c, rays, hits, n, surfaces, materials, (hipStream_t)stream, false);
+}
+
+rt_status rt_shade_hits(rt_ctx* c, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                        const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths,
+                        rt_ray* next_rays, rt_ray* shadow_rays, float* contrib) {
+    return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib, nullptr, true);
+}
+
+rt_status rt_shade_hits_on(rt_ctx* c, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                           const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths,
+                           rt_ray* next_rays, rt_ray* shadow_rays, float* contrib, void* stream) {
+    return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib,
+                 (hipStream_t)stream, false);
 }
 
 rt_status rt_get_query_stats(rt_ctx* c, rt_query_stats* out) {

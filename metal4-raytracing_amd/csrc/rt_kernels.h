@@ -153,6 +153,27 @@ struct RsParams {
 unsigned resolve_resident_blocks();
 void launch_resolve(const DevScene& S, const RsParams& P, unsigned blocks, hipStream_t stream);
 
+// Shading queries (rq_shade, rt_query.hip): one thread per record turns the traced ray's direction,
+// its surface and material records and the path state into the updated path, the next ray, the
+// shadow ray and its contribution, by scatter_eval (rt_scatter.h).  Lights and the Halton table
+// are the context's; nothing else of the scene is read.
+struct ShParams {
+    const float4* rays;        // two words per record (rt_ray); the second is read
+    const float4* surfaces;    // four words per record (rt_surface)
+    const float4* materials;   // three (rt_surface_material)
+    const float4* randoms;     // two, or null: the renderer's Halton numbers
+    float4* paths;             // three (rt_path), in place
+    float4* next_rays;         // two; may alias rays
+    float4* shadow_rays;       // two
+    float4* contrib;           // one
+    const Light* lights;
+    const HaltonDim* halton;
+    uint32_t n;
+    int shading_mode, max_bounces, light_count;
+};
+unsigned shade_resident_blocks();
+void launch_shade(const ShParams& P, unsigned blocks, hipStream_t stream);
+
 // Utility kernels (rt_util.hip)
 // G-buffer-guided denoise for RT_SCALER_DENOISED (rt_present.hip); returns tmp0 or tmp1, whichever
 // holds the result (passes = 0 returns the demodulated radiance unremodulated: callers pass >= 1)

@@ -97,6 +97,28 @@ static constexpr int RT_MAX_BOUNCES = 12;
 // is identical to n / b, so the float sequence is identical to the reference loop.
 struct HaltonDim { uint32_t b; uint32_t m; uint32_t sh; float invB; };
 
+// The first n entries of the table (host): the primes in order with their division constants.
+// What rt_create uploads and rt_debug_shade_host reads.
+inline void halton_table_fill(HaltonDim* t, int n) {
+    int have = 0;
+    for (uint32_t c = 2; have < n; ++c) {
+        bool prime = true;
+        for (int k = 0; k < have; ++k) {
+            if (t[k].b * t[k].b > c) break;
+            if (c % t[k].b == 0) { prime = false; break; }
+        }
+        if (!prime) continue;
+        HaltonDim h;
+        h.b = c;
+        uint32_t l = 0;
+        while ((1u << l) < c) ++l;              // 2^(l-1) < b <= 2^l
+        h.m = (uint32_t)(((1ull << (31 + l)) + c - 1) / c);
+        h.sh = l - 1;
+        h.invB = 1.0f / (float)c;
+        t[have++] = h;
+    }
+}
+
 RT_HD uint32_t umulhi32(uint32_t a, uint32_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __umulhi(a, b);

@@ -1,10 +1,13 @@
 // rt_query.hip — device ray queries (rt_trace_closest / rt_trace_any, include/rt_api.h): the
 // caller's rays traced against the built scene by one persistent launch, built from the stepwise
 // traversal of rt_trav.h the way wf_trace (rt_wavefront.hip) is.  The replacement of Metal's
-// `intersector.intersect` called from a kernel other than raytracingKernel.
+// `intersector.intersect` called from a kernel other than raytracingKernel.  Next to it the two
+// per-record kernels of a user-side integrator: rq_resolve (rt_resolve_hits) and rq_shade
+// (rt_shade_hits).
 #include <hip/hip_runtime.h>
 
 #include "rt_kernels.h"
+#include "rt_scatter.h"
 #include "rt_surface.h"
 #include "rt_trav.h"
 #include "rt_wf_queue.h"   // lane_id, mbcnt64
@@ -136,7 +139,65 @@ __global__ void __launch_bounds__(kBlock) rq_resolve(DevScene S, RsParams P) {
     }
 }
 
+// ---- shading queries: a resolved hit and its path state -> the path's next rays ---------------------
+// One record per thread, grid-stride over at most the resident blocks, as rq_resolve.  Per record
+// eleven 16-B loads (the ray's direction word, four of the surface, three of the material, three
+// of the path; two more with the caller's numbers) and eight 16-B stores (path, next ray, shadow
+// ray, contribution).  The Halton dimensions and the lights are read from global memory: a record
+// draws at most four dimensions (16 B each) chosen by its own step, glass paths reach dimensions
+// past the 64 an LDS copy would hold, and the whole table is 16 KB, cache resident after the first
+// wave; staging tables per block would cost small batches more than it saves (rq_resolve's choice).
+// No LDS, no atomics.  next_rays may alias rays: a thread reads its record before it writes it.
+template <bool RANDOMS>
+__global__ void __launch_bounds__(kBlock) rq_shade(ShParams P) {
+    const ScatterOpts U{P.shading_mode, P.max_bounces, P.light_count};
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)P.n; i += stride) {
+        const float4 d4 = P.rays[2 * i + 1];
+        const float4* const sp = P.surfaces + 4 * i;
+        const float4 s0 = sp[0], s1 = sp[1], s2 = sp[2];
+        const uint4 s3 = reinterpret_cast<const uint4*>(sp)[3];
+        const float4* const mp = P.materials + 3 * i;
+        const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
+        float4* const pp = P.paths + 3 * i;
+        PathWords w;
+        w.p0 = pp[0];
+        w.p1 = pp[1];
+        w.p2 = reinterpret_cast<const int4*>(pp)[2];
+        float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+        if (RANDOMS) {
+            r0 = P.randoms[2 * i];
+            r1 = P.randoms[2 * i + 1];
+        }
+        ScatterOut o;
+        scatter_eval<RANDOMS>(P.halton, P.lights, U, d4, s0, s1, s2, s3, m0, m1, m2, r0, r1, w, o);
+        pp[0] = w.p0;
+        pp[1] = w.p1;
+        reinterpret_cast<int4*>(pp)[2] = w.p2;
+        P.next_rays[2 * i] = o.n0;
+        P.next_rays[2 * i + 1] = o.n1;
+        P.shadow_rays[2 * i] = o.h0;
+        P.shadow_rays[2 * i + 1] = o.h1;
+        P.contrib[i] = o.c;
+    }
+}
+
 }  // namespace
+
+unsigned shade_resident_blocks() {
+    static const unsigned resident = [] {
+        int dev = 0, cus = 256, per = 0;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rq_shade<false>, kBlock, 0) != hipSuccess || per < 1) per = 4;
+        return (unsigned)(cus * per);
+    }();
+    return resident;
+}
+
+void launch_shade(const ShParams& P, unsigned blocks, hipStream_t stream) {
+    auto kernel = P.randoms ? rq_shade<true> : rq_shade<false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, P);
+}
 
 unsigned resolve_resident_blocks() {
     static const unsigned resident = [] {

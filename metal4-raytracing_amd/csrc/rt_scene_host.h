@@ -51,6 +51,31 @@ inline rt_status validate_scene(rt_ctx* c, const rt_scene_desc* sd, int& max_sub
     return RT_OK;
 }
 
+// What rt_shade_hits and rt_debug_shade_host accept of their arguments before they look at the
+// lights: opts in range, every pointer but `randoms` set when n > 0, all of them 16-byte aligned.
+inline rt_status validate_shade(rt_ctx* c, const rt_shade_opts* o, const void* rays, const void* surfaces,
+                                const void* materials, const void* randoms, uint32_t n, const void* paths,
+                                const void* next_rays, const void* shadow_rays, const void* contrib) {
+    if (!o) FAIL(c, RT_ERR_INVALID_ARG, "null opts");
+    if (o->shading_mode != ShadingModePBR && o->shading_mode != ShadingModeLegacy)
+        FAIL(c, RT_ERR_INVALID_ARG, "shading_mode is neither ShadingModePBR nor ShadingModeLegacy");
+    if (o->max_bounces < 1 || o->max_bounces > RT_MAX_BOUNCES) FAIL(c, RT_ERR_INVALID_ARG, "max_bounces outside 1 .. 12");
+    if (o->light_count < 0) FAIL(c, RT_ERR_INVALID_ARG, "negative light_count");
+    if (n > 0 && (!rays || !surfaces || !materials || !paths || !next_rays || !shadow_rays || !contrib))
+        FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+    if (((uintptr_t)rays | (uintptr_t)surfaces | (uintptr_t)materials | (uintptr_t)randoms | (uintptr_t)paths |
+         (uintptr_t)next_rays | (uintptr_t)shadow_rays | (uintptr_t)contrib) & 15u)
+        FAIL(c, RT_ERR_INVALID_ARG, "every record array must be 16-byte aligned");
+    return RT_OK;
+}
+// opts->light_count against the lights there are: 0 = all of them.
+inline rt_status shade_light_count(rt_ctx* c, const rt_shade_opts* o, uint32_t have, int& count) {
+    count = o->light_count ? o->light_count : (int)have;
+    if (count < 1) FAIL(c, RT_ERR_INVALID_ARG, "no lights");
+    if ((uint32_t)count > have) FAIL(c, RT_ERR_INVALID_ARG, "light_count above the lights there are");
+    return RT_OK;
+}
+
 // A scene description flattened mesh by mesh: positions and normals with every mesh's vertices
 // after the previous one's, triangles as (three vertex ids, mesh << 8 | submesh), 12 floats of
 // transform per mesh.  nrm may be null.

@@ -19,7 +19,17 @@ timed runs each child does one counting run for the node visits and triangle tes
     beside it) and as the fraction of the HBM floor: 64 B of ray and hit in, the 64-B tri_nrm line
     and 64 B (112 B with materials) out per record, at 6.3 TB/s.
 
-    python tools/query_bench.py [--resolve] [--scene c3g] [--width 1920] [--height 1080] [--run-timeout 60]
+--shade runs legs (c, with materials) and (d) in one child and prints one JSON line:
+(d) shade: Renderer.shade on the rays, surface and material records of (c) with fresh camera
+    paths (throughput 1, bounce 0, Halton index = the ray's number mod 2^20; restored from a copy
+    before every run, outside the timed span), the Renderer's default uniforms (PBR, 2 bounces),
+    timed the same way.  Reported as records per second and as the fraction of the HBM floor:
+    16 B of ray direction, 64 B of surface, 48 B of material and 48 B of path in, 48 B of path,
+    two 32-B rays and 16 B of contribution out per record (304 B), at 6.3 TB/s.  Then the same
+    launch with the caller's numbers (uniform random, 32 B more per record: 336 B) in place of the
+    Halton draws, which tells the cost of the Halton digit loops from that of the traffic.
+
+    python tools/query_bench.py [--resolve | --shade] [--scene c3g] [--width 1920] [--height 1080] [--run-timeout 60]
 """
 import argparse
 import importlib
@@ -152,6 +162,51 @@ def child_resolve(args):
     return 0
 
 
+SHADE_BYTES = (16 + 64 + 48 + 48) + (48 + 32 + 32 + 16)   # compulsory bytes per record of leg (d)
+
+
+def child_shade(args):
+    rt = _rt()
+    import torch
+    W, H = args.width, args.height
+    R = rt.Renderer(rt.Scene.preset(args.scene), 64, 64)
+    dev = torch.device("cuda", 0)
+    rays = camera_rays(rt, W, H, dev)
+    n = rays.shape[0]
+    hits = R.trace(rays)
+    R.wait()
+    surf = torch.empty((n, 16), dtype=torch.float32, device=dev)
+    mat = torch.empty((n, 12), dtype=torch.float32, device=dev)
+    fresh = rt.Renderer.make_paths(torch.arange(n, device=dev) % (1 << 20)).buffer
+    paths = fresh.clone()
+    out = (torch.empty((n, 8), dtype=torch.float32, device=dev), torch.empty((n, 8), dtype=torch.float32, device=dev),
+           torch.empty((n, 4), dtype=torch.float32, device=dev))
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.synchronize()
+    nhit = int((hits.triangle != -1).sum().item())
+    _emit(ready=True)
+    S = None
+    rnd = torch.rand((n, 8), generator=torch.Generator(device=dev).manual_seed(1), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    for kind in ("surface_material", "shade", "shade_randoms"):
+        for k in range(WARMUP + RUNS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(stream):
+                paths.copy_(fresh)
+            e0.record(stream)
+            if kind != "surface_material":
+                R.shade(rays, S, paths, randoms=rnd if kind == "shade_randoms" else None, out=out, stream=stream.cuda_stream)
+            else:
+                S = R.resolve(rays, hits, out=(surf, mat), stream=stream.cuda_stream)
+            e1.record(stream)
+            e1.synchronize()
+            _emit(run=k, kind=kind, records=n, hits=nhit, ms=float(e0.elapsed_time(e1)))
+    P = rt.Paths(paths, paths.view(torch.int32))
+    _emit(shaded=True, alive=int(P.alive.sum().item()), shadow=int(P.shadow.sum().item()))
+    R.close()
+    return 0
+
+
 def run_child(kind, args):
     """The child's reports; every line has to arrive within its time limit."""
     cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--scene", args.scene, "--width", str(args.width),
@@ -200,14 +255,17 @@ def main():
     ap.add_argument("--run-timeout", type=float, default=60.0, help="seconds each run may take")
     ap.add_argument("--setup-timeout", type=float, default=240.0, help="seconds the scene load and BVH build may take")
     ap.add_argument("--resolve", action="store_true", help="leg (c) only: the surface query on leg (b)'s hits")
-    ap.add_argument("--child", choices=["frame", "query", "resolve"])
+    ap.add_argument("--shade", action="store_true", help="legs (c, with materials) and (d): the shading query on (c)'s records")
+    ap.add_argument("--child", choices=["frame", "query", "resolve", "shade"])
     args = ap.parse_args()
     if args.child:
-        return {"frame": child_frame, "query": child_query, "resolve": child_resolve}[args.child](args)
+        return {"frame": child_frame, "query": child_query, "resolve": child_resolve, "shade": child_shade}[args.child](args)
     res = {"scene": args.scene, "width": args.width, "height": args.height, "rays": args.width * args.height * 4}
-    if args.resolve:
-        lines, err = run_child("resolve", args)
-        for kind, nbytes in RESOLVE_BYTES.items():
+    if args.resolve or args.shade:
+        lines, err = run_child("shade" if args.shade else "resolve", args)
+        legs = {"surface_material": RESOLVE_BYTES["surface_material"], "shade": SHADE_BYTES,
+                "shade_randoms": SHADE_BYTES + 32} if args.shade else RESOLVE_BYTES
+        for kind, nbytes in legs.items():
             runs = [r for r in lines if r.get("kind") == kind and r["run"] >= WARMUP]
             if not err and len(runs) != RUNS:
                 err = f"resolve ({kind}): {len(runs)} timed runs reported, not {RUNS}"
@@ -221,7 +279,12 @@ def main():
             res[f"{kind}_ms"] = statistics.median(r["ms"] for r in runs)
             res[f"{kind}_floor_ghits"] = round(HBM_BYTES_PER_S / nbytes * 1e-9, 2)
             res[f"{kind}_floor_fraction"] = round(res[f"{kind}_ghits"] * 1e9 * nbytes / HBM_BYTES_PER_S, 4)
+            res[f"{kind}_floor_bytes"] = nbytes
             res["hit_share"] = round(runs[-1]["hits"] / runs[-1]["records"], 4)
+        for r in lines:
+            if r.get("shaded"):
+                res["shade_alive_share"] = round(r["alive"] / res["rays"], 4)
+                res["shade_shadow_share"] = round(r["shadow"] / res["rays"], 4)
         print(json.dumps(res))
         return 0
     for kind in ("frame", "query"):
