@@ -1,45 +1,34 @@
-// rt_scatter.h — a shading query: one resolved hit and its path state turned into the path's next
-// ray, its shadow ray and the updated state (rt_shade_hits, include/rt_api.h).
+// rt_scatter.h — the scatter half of a hit: everything raytracingKernel does with a surface point
+// once it has one (Raytracing.metal:517-774): glass, the light pick, the four light types, the
+// legacy and GGX direct terms, the cosine bounce and the bounce / step bookkeeping.
 //
-// scatter_step states the expressions of shade_step (rt_shade.h, :317-474 there: everything after
-// the material fetch) in the same order on the same operands, so every float equals the one a
-// frame kernel forms at that hit with the same path state, bit for bit.  Its inputs are the
-// records surface_eval (rt_surface.h) wrote: P, Ng, the shading normal, the albedo, the clamped
-// opacity, the emission, max(ior, 1), roughness and metallic.  shade_step itself does not call it
-// (LDS tables, tuned register counts: see rt_surface.h); tests/test_gpu_shade.py pins the two
-// against each other through whole frames re-assembled from queries.  Compiled for gfx950
-// (rq_shade, rt_query.hip) and for the host (rt_debug_shade_host).
+// scatter_step is the one text of it.  shade_step (rt_shade.h) calls it for the frame kernels;
+// scatter_eval, below, calls it for a shading query (rq_shade, rt_query.hip) and for the host hook
+// (rt_debug_shade_host) on the records surface_eval (rt_surface.h) wrote.  The callers differ in
+// two things only, which a draw policy answers: where random number D of step s of path i comes
+// from, and where light record k lies.  Same function, same operands: the floats are equal bit
+// for bit by construction, and what tests/test_gpu_shade.py pins through whole frames re-assembled
+// from queries is the seam (the policies, the LDS tables against the global ones, the record
+// packing).
 #pragma once
 #include "rt_surface.h"
 
 namespace rt {
 
-// rt_shade_opts with the light count resolved (0 = every uploaded light) and checked by the host.
-struct ScatterOpts {
-    int shadingMode, maxBounces, lightCount;
+struct PathRegs {
+    f3 color;
+    f3 accum;
+    int bounce, step, tpass;
 };
 
-// rt_path as 16-B words: (throughput, sample), (radiance, flags), (bounce, step, passes, reserved).
-struct PathWords {
-    float4 p0, p1;
-    int4 p2;
-};
-
-// The three output records: next ray (origin, direction | tmax), shadow ray, contribution.
-struct ScatterOut {
-    float4 n0, n1, h0, h1, c;
-};
-
-// The renderer's Halton number (halton of rt_shade.h's ShadeTabs) from the global table.  Every
-// dimension drawn here is >= 2, so the base-2 closed form never applies.  The dimension is
-// clamped to the table: a no-op for every state the renderer reaches (step <= 156, dimension
-// <= 943), it keeps a caller's step from indexing outside the table.
-RT_HD float scatter_halton(const HaltonDim* tab, int i, int step, uint32_t stride, uint32_t k) {
-    const uint32_t d = 2u + (uint32_t)step * stride + k;
-    return halton_fast(i, tab[d < (uint32_t)RT_HALTON_DIMS ? d : (uint32_t)(RT_HALTON_DIMS - 1)]);
+// The six random numbers a step may draw, and the Halton dimension of each:
+// 2 + step * stride + offset (Raytracing.metal:540, :588, :599-600, :763-764).  In unsigned
+// arithmetic: a query's step is the caller's.
+enum Draw { kDrawLight, kDrawAreaU, kDrawAreaV, kDrawGlass, kDrawBounce0, kDrawBounce1 };
+RT_HD uint32_t draw_dim(Draw d, int step) {
+    constexpr uint32_t stride[6] = {6u, 6u, 6u, 6u, 5u, 5u}, offset[6] = {0u, 1u, 2u, 5u, 3u, 4u};
+    return 2u + (uint32_t)step * stride[d] + offset[d];
 }
-
-RT_HD f3 ld3l(const rt_float3& v) { return mk3(v.x, v.y, v.z); }   // rt_shade.h's ldf3, for the host too
 
 // min((int)(x * count), count - 1) of :588-589, with anything below 0 or NaN -> 0 and anything
 // from count up -> count - 1 decided on the float: the same index for x in [0, 1), never one
@@ -50,17 +39,18 @@ RT_HD int scatter_light_index(float x, int count) {
     return v < (float)count ? (int)v : count - 1;
 }
 
-// shade_step from :317 on.  rayO / rayD, color / accum, bounce / step / tpass are the renderer's
-// registers; rnd0 = (light, area u, area v, glass choice), rnd1 = (r0, r1, -, -) replace the
-// Halton numbers when RANDOMS.  Returns shade_step's r.next.
-template <bool RANDOMS>
-RT_HD bool scatter_step(const HaltonDim* tab, const Light* lights, const ScatterOpts& U, int hidx, const float4 rnd0,
-                        const float4 rnd1, f3 P_, f3 Ng, f3 shadingNormal, f3 albedo, float opacity, f3 emission,
-                        float ior_in, float roughness, float metallic, f3& rayO, f3& rayD, PathRegs& p, bool& shadow,
-                        f3& so, f3& sd, float& stmax, f3& contrib) {
+// Raytracing.metal:517-774 at surface point s with shading normal shadingNormal.  rayO / rayD (in:
+// the ray that hit; out: the next ray), color / accum, bounce / step / tpass are the renderer's
+// registers.  draws.draw(D, i, step) is random number D of step `step` of Halton index i,
+// draws.light(k) light record k; U carries shadingMode, maxBounces and lightCount.  Sets shadow
+// and the shadow ray (so, sd, stmax) with its contribution when the step emits one, and leaves
+// them alone otherwise.  Returns whether the path goes on with rayO / rayD.
+template <class DRAWS, class OPTS>
+RT_HD bool scatter_step(const DRAWS& draws, const OPTS& U, int hidx, const SurfacePoint& s, f3 shadingNormal, f3& rayO,
+                        f3& rayD, PathRegs& p, bool& shadow, f3& so, f3& sd, float& stmax, f3& contrib) {
     const float ao = 1.0f;                                                            // :443-446 (ENABLE_AO 0)
-    float clampedOpacity = clampf(opacity, 0.0f, 1.0f);                              // :517-576
-    float ior = fmaxf(ior_in, 1.0f);
+    float clampedOpacity = clampf(s.opacity, 0.0f, 1.0f);                            // :517-576
+    float ior = fmaxf(s.ior, 1.0f);
     if (clampedOpacity < 0.999f || ior > 1.01f) {
         f3 N = shadingNormal, I = rayD;
         float cosi = clampf(dot(-I, N), -1.0f, 1.0f);
@@ -82,19 +72,19 @@ RT_HD bool scatter_step(const HaltonDim* tab, const Light* lights, const Scatter
         float refractWeight = (1.0f - F) * transmission;
         float totalWeight = fmaxf(reflectWeight + refractWeight, 1e-4f);
         float reflectProb = reflectWeight / totalWeight;
-        float choice = RANDOMS ? rnd0.w : scatter_halton(tab, hidx, p.step, 6u, 5u);
+        float choice = draws.draw(kDrawGlass, hidx, p.step);
         bool consumeBounce = true;
         if (k < 0.0f || choice < reflectProb) {
             f3 reflectDir = normalize(I - (2.0f * dot(I, N)) * N);
-            rayO = P_ + reflectDir * 1e-3f;
+            rayO = s.P + reflectDir * 1e-3f;
             rayD = reflectDir;
             p.color = p.color * totalWeight;
         } else {
             float cosT = sqrtf(fmaxf(k, 0.0f));
             f3 refractDir = normalize(eta * I + (eta * cosi - cosT) * N);
-            rayO = P_ + refractDir * 1e-3f;
+            rayO = s.P + refractDir * 1e-3f;
             rayD = refractDir;
-            p.color = p.color * (totalWeight * albedo);
+            p.color = p.color * (totalWeight * s.albedo);
             consumeBounce = false;
         }
         p.step++;
@@ -111,59 +101,57 @@ RT_HD bool scatter_step(const HaltonDim* tab, const Light* lights, const Scatter
         return p.bounce < U.maxBounces;
     }
 
-    float perceptualRoughness = clampf(roughness, 0.04f, 1.0f);                       // :578-582
+    float perceptualRoughness = clampf(s.roughness, 0.04f, 1.0f);                     // :578-582
     float alpha = perceptualRoughness * perceptualRoughness;
-    f3 diffuseColor = albedo;
-    f3 F0 = mix3(mk3(0.04f, 0.04f, 0.04f), albedo, metallic);
+    f3 diffuseColor = s.albedo;
+    f3 F0 = mix3(mk3(0.04f, 0.04f, 0.04f), s.albedo, s.metallic);
     f3 V = normalize(-rayD);
 
-    p.accum = p.accum + p.color * emission;                                           // :585
+    p.accum = p.accum + p.color * s.emission;                                         // :585
 
-    float lightSample = RANDOMS ? rnd0.x : scatter_halton(tab, hidx, p.step, 6u, 0u);   // :588-591
-    int lightIndex = scatter_light_index(lightSample, U.lightCount);
-    const Light& light = lights[lightIndex];
+    float lightSample = draws.draw(kDrawLight, hidx, p.step);                         // :588-591
+    const Light& light = draws.light(scatter_light_index(lightSample, U.lightCount));
     f3 Ldir, lightColor;
     float lightDistance;
-    f3 lpos = ld3l(light.position), lcol = ld3l(light.color);
+    f3 lpos = ldf3(light.position), lcol = ldf3(light.color);
     if (light.type == LightTypeAreaLight) {                                           // :597-606, :95-129
-        float ux = RANDOMS ? rnd0.y : scatter_halton(tab, hidx, p.step, 6u, 1u);
-        float uy = RANDOMS ? rnd0.z : scatter_halton(tab, hidx, p.step, 6u, 2u);
+        float ux = draws.draw(kDrawAreaU, hidx, p.step), uy = draws.draw(kDrawAreaV, hidx, p.step);
         ux = ux * 2.0f - 1.0f;
         uy = uy * 2.0f - 1.0f;
-        f3 sp = (lpos + ld3l(light.right) * ux) + ld3l(light.up) * uy;
-        Ldir = sp - P_;
+        f3 sp = (lpos + ldf3(light.right) * ux) + ldf3(light.up) * uy;
+        Ldir = sp - s.P;
         lightDistance = length(Ldir);
         float inv = 1.0f / fmaxf(lightDistance, 1e-3f);
         Ldir = Ldir * inv;
         lightColor = lcol * (inv * inv);
-        lightColor = lightColor * saturate(dot(-Ldir, ld3l(light.forward)));
+        lightColor = lightColor * saturate(dot(-Ldir, ldf3(light.forward)));
     } else if (light.type == LightTypeSpotlight) {                                    // :608-632
-        Ldir = lpos - P_;
+        Ldir = lpos - s.P;
         lightDistance = length(Ldir);
         float inv = 1.0f / fmaxf(lightDistance, 1e-3f);
         Ldir = Ldir * inv;
         lightColor = mk3(0.0f, 0.0f, 0.0f);
-        f3 coneDirection = normalize(ld3l(light.direction));
+        f3 coneDirection = normalize(ldf3(light.direction));
         float spotResult = dot(-Ldir, coneDirection);
         if (spotResult > cos_pinned(light.coneAngle)) lightColor = (lcol * inv) * inv;
     } else if (light.type == LightTypePointlight) {                                   // :633-638
-        Ldir = lpos - P_;
+        Ldir = lpos - s.P;
         lightDistance = length(Ldir);
         float inv = 1.0f / fmaxf(lightDistance, 1e-3f);
         Ldir = Ldir * inv;
         lightColor = (lcol * inv) * inv;
     } else {                                                                          // :639-643
-        Ldir = -normalize(ld3l(light.direction));
+        Ldir = -normalize(ldf3(light.direction));
         lightDistance = INFINITY;
         lightColor = lcol;
     }
     lightColor = lightColor * (float)U.lightCount;                                    // :647
-    f3 origin = P_ + Ng * 1e-3f;                                                      // :660, :683, :720, :769
+    f3 origin = s.P + s.Ng * 1e-3f;                                                   // :660, :683, :720, :769
 
     if (U.shadingMode == ShadingModeLegacy) {                                         // :649-690
         f3 L = normalize(Ldir);
         float NdotL = saturate(dot(shadingNormal, L));
-        f3 legacyColor = p.color * albedo;
+        f3 legacyColor = p.color * s.albedo;
         if (length_lt_1e3(legacyColor)) return false;
         if (length_gt_1e4(lightColor) && NdotL > 0.0f) {
             shadow = true;
@@ -174,43 +162,33 @@ RT_HD bool scatter_step(const HaltonDim* tab, const Light* lights, const Scatter
         }
         p.color = legacyColor * ao;
         if (length_lt_1e3(p.color)) return false;
-        float r0 = RANDOMS ? rnd1.x : scatter_halton(tab, hidx, p.step, 5u, 3u);
-        float r1 = RANDOMS ? rnd1.y : scatter_halton(tab, hidx, p.step, 5u, 4u);
-        rayD = alignHemisphereWithNormal(sampleCosineWeightedHemisphere(r0, r1), shadingNormal);
-        rayO = origin;
-        p.step++;
-        p.bounce++;
-        p.tpass = 0;
-        return p.bounce < U.maxBounces;
+    } else {
+        if (length_gt_1e4(lightColor)) {                                              // :692-744
+            f3 L = normalize(Ldir);
+            f3 H = normalize(V + L);
+            float NdotL = saturate(dot(shadingNormal, L));
+            float NdotV = saturate(dot(shadingNormal, V));
+            float NdotH = saturate(dot(shadingNormal, H));
+            float VdotH = saturate(dot(V, H));
+            f3 F = fresnelSchlick(VdotH, F0);
+            float D = distributionGGX(NdotH, alpha);
+            float kk = perceptualRoughness + 1.0f;
+            kk = (kk * kk) / 8.0f;
+            float G = geometrySmith(NdotV, NdotL, kk);
+            f3 specular = ((D * G) * F) / fmaxf((4.0f * NdotV) * NdotL, 1e-4f);
+            f3 kD = (mk3(1.0f, 1.0f, 1.0f) - F) * (1.0f - s.metallic);
+            f3 diffuse = (kD * diffuseColor) / RT_PI;
+            f3 direct = ((diffuse + specular) * lightColor) * NdotL;
+            shadow = true;
+            so = origin;
+            sd = Ldir;
+            stmax = lightDistance - 1e-3f;
+            contrib = p.color * direct;
+        }
+        p.color = p.color * ((diffuseColor * (1.0f - s.metallic)) * ao);              // :748
+        if (length_lt_1e3(p.color)) return false;                                     // :751-753
     }
-
-    if (length_gt_1e4(lightColor)) {                                                  // :692-744
-        f3 L = normalize(Ldir);
-        f3 H = normalize(V + L);
-        float NdotL = saturate(dot(shadingNormal, L));
-        float NdotV = saturate(dot(shadingNormal, V));
-        float NdotH = saturate(dot(shadingNormal, H));
-        float VdotH = saturate(dot(V, H));
-        f3 F = fresnelSchlick(VdotH, F0);
-        float D = distributionGGX(NdotH, alpha);
-        float kk = perceptualRoughness + 1.0f;
-        kk = (kk * kk) / 8.0f;
-        float G = geometrySmith(NdotV, NdotL, kk);
-        f3 specular = ((D * G) * F) / fmaxf((4.0f * NdotV) * NdotL, 1e-4f);
-        f3 kD = (mk3(1.0f, 1.0f, 1.0f) - F) * (1.0f - metallic);
-        f3 diffuse = (kD * diffuseColor) / RT_PI;
-        f3 direct = ((diffuse + specular) * lightColor) * NdotL;
-        shadow = true;
-        so = origin;
-        sd = Ldir;
-        stmax = lightDistance - 1e-3f;
-        contrib = p.color * direct;
-    }
-
-    p.color = p.color * ((diffuseColor * (1.0f - metallic)) * ao);                    // :748
-    if (length_lt_1e3(p.color)) return false;                                         // :751-753
-    float r0 = RANDOMS ? rnd1.x : scatter_halton(tab, hidx, p.step, 5u, 3u);      // :763-764
-    float r1 = RANDOMS ? rnd1.y : scatter_halton(tab, hidx, p.step, 5u, 4u);
+    float r0 = draws.draw(kDrawBounce0, hidx, p.step), r1 = draws.draw(kDrawBounce1, hidx, p.step);   // :683-684, :763-764
     rayD = alignHemisphereWithNormal(sampleCosineWeightedHemisphere(r0, r1), shadingNormal);
     rayO = origin;                                                                    // :769-770
     p.step++;
@@ -218,6 +196,52 @@ RT_HD bool scatter_step(const HaltonDim* tab, const Light* lights, const Scatter
     p.tpass = 0;
     return p.bounce < U.maxBounces;
 }
+
+// ---- shading queries --------------------------------------------------------------------------
+
+// rt_shade_opts with the light count resolved (0 = every uploaded light) and checked by the host.
+struct ScatterOpts {
+    int shadingMode, maxBounces, lightCount;
+};
+
+// The query's draw policy: the renderer's Halton numbers from the global table, or the caller's
+// when RANDOMS, rnd0 = (light, area u, area v, glass choice), rnd1 = (r0, r1, -, -); the lights
+// from global memory.  Every dimension drawn is >= 2, so the base-2 closed form of the frames'
+// table (ShadeTabs, rt_shade.h) never applies.  The dimension is clamped to the table: a no-op for
+// every state the renderer reaches (step <= 156, dimension <= 943), it keeps a caller's step from
+// indexing outside the table.
+template <bool RANDOMS>
+struct QueryDraws {
+    const HaltonDim* tab;
+    const Light* lights;
+    float4 rnd0, rnd1;
+    __host__ __device__ __forceinline__ float draw(Draw d, int i, int step) const {
+        if (RANDOMS) {
+            switch (d) {
+                case kDrawLight: return rnd0.x;
+                case kDrawAreaU: return rnd0.y;
+                case kDrawAreaV: return rnd0.z;
+                case kDrawGlass: return rnd0.w;
+                case kDrawBounce0: return rnd1.x;
+                default: return rnd1.y;
+            }
+        }
+        const uint32_t dim = draw_dim(d, step);
+        return halton_fast(i, tab[dim < (uint32_t)RT_HALTON_DIMS ? dim : (uint32_t)(RT_HALTON_DIMS - 1)]);
+    }
+    __host__ __device__ __forceinline__ const Light& light(int k) const { return lights[k]; }
+};
+
+// rt_path as 16-B words: (throughput, sample), (radiance, flags), (bounce, step, passes, reserved).
+struct PathWords {
+    float4 p0, p1;
+    int4 p2;
+};
+
+// The three output records: next ray (origin, direction | tmax), shadow ray, contribution.
+struct ScatterOut {
+    float4 n0, n1, h0, h1, c;
+};
 
 // One record of rt_shade_hits.  d4: the traced ray's direction word; s0..s3 / m0..m2: its
 // rt_surface and rt_surface_material; rnd0 / rnd1: the caller's numbers (RANDOMS).  Updates the
@@ -243,13 +267,21 @@ RT_HD void scatter_eval(const HaltonDim* tab, const Light* lights, const Scatter
     p.bounce = w.p2.x;
     p.step = w.p2.y;
     p.tpass = w.p2.z;
+    SurfacePoint s;   // the fields scatter_step reads
+    s.P = ld3(s0);
+    s.Ng = ld3(s1);
+    s.albedo = ld3(m0);
+    s.opacity = m0.w;
+    s.emission = ld3(m1);
+    s.ior = m1.w;
+    s.roughness = m2.x;
+    s.metallic = m2.y;
     f3 rayO = mk3(0.0f, 0.0f, 0.0f), rayD = ld3(d4);
     bool shadow = false;
     f3 so = rayO, sd = rayO, contrib = rayO;
     float stmax = -1.0f;
-    const bool next = scatter_step<RANDOMS>(tab, lights, U, (int)f2u(w.p0.w), rnd0, rnd1, ld3(s0), ld3(s1), ld3(s2),
-                                            ld3(m0), m0.w, ld3(m1), m1.w, m2.x, m2.y, rayO, rayD, p, shadow, so, sd,
-                                            stmax, contrib);
+    const QueryDraws<RANDOMS> draws{tab, lights, rnd0, rnd1};
+    const bool next = scatter_step(draws, U, (int)f2u(w.p0.w), s, ld3(s2), rayO, rayD, p, shadow, so, sd, stmax, contrib);
     if (next) {
         flags |= RT_PATH_ALIVE;
         o.n0 = make_float4(rayO.x, rayO.y, rayO.z, 0.0f);

@@ -1,6 +1,6 @@
 """Shared by tests/test_surface_host.py and tests/test_gpu_surface.py (no tests here): the camera
 rays of a frame restated in float32 numpy, and the surface / material records of a batch of hits
-restated from the scene descriptor.  Every expression keeps the operand order of csrc/rt_shade.h
+restated from the scene descriptor.  Every expression keeps the operand order of csrc/rt_surface.h
 and csrc/rt_math.h (numpy's float32 + - * / sqrt are the IEEE operations, nothing is contracted),
 so the results are compared bitwise."""
 import ctypes as C
@@ -150,7 +150,7 @@ def restate(A, osc, o, d, t, ids, u, v):
             emis[k] = sample(k, 5, True)[:3]
     opac = _clamp01(opac)
     ior = np.maximum(A.ior[ids], F(1))
-    # computeTangentBasis' validity (csrc/rt_shade.h tangent_basis), for RT_SURFACE_NORMAL_MAPPED
+    # computeTangentBasis' validity (csrc/rt_surface.h tangent_basis), for RT_SURFACE_NORMAL_MAPPED
     p0, p1, p2 = A.pos[i1], A.pos[i2], A.pos[i0]
     e1, e2 = p1 - p0, p2 - p0
     d1x, d1y, d2x, d2y = b[:, 0] - a[:, 0], b[:, 1] - a[:, 1], c[:, 0] - a[:, 0], c[:, 1] - a[:, 1]
