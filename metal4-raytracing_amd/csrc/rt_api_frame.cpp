@@ -67,6 +67,7 @@ rt_status ensure_wavefront(rt_ctx* c, FrameSlot& fs, size_t own_px, int spp, int
     if (W.cap_paths < paths || W.queue_entries < wavefront_queue_entries(paths, max_extra)) {
         size_t qe = wavefront_queue_entries(paths, max_extra);
         if ((st = dev_alloc(c, fs.qc, 2 * qe * 16))) return st;   // both queues' colour arrays
+        if ((st = dev_alloc(c, fs.qr, 2 * qe * 4))) return st;    // ... root-word arrays
         if ((st = dev_alloc(c, fs.accum, paths * 16))) return st;
         if ((st = dev_alloc(c, fs.meta, paths * 16))) return st;
         if ((st = dev_alloc(c, fs.q0, qe * 32))) return st;
@@ -104,6 +105,8 @@ rt_status ensure_wavefront(rt_ctx* c, FrameSlot& fs, size_t own_px, int spp, int
     }
     W.qc[0] = (float4*)fs.qc.p;
     W.qc[1] = (float4*)fs.qc.p + W.queue_entries;
+    W.qr[0] = (uint32_t*)fs.qr.p;
+    W.qr[1] = (uint32_t*)fs.qr.p + W.queue_entries;
     W.p_accum = (float4*)fs.accum.p;
     W.p_meta = (uint4*)fs.meta.p;
     W.q[0] = (float4*)fs.q0.p;

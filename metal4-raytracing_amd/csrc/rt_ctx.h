@@ -27,7 +27,7 @@ struct MeshInfo {
 // the slots (rt::FrameRing) and overlap except where frame f needs frame f-1's results (the history
 // target and the previous motion vectors: the extra-sample pass and the resolve).
 struct FrameSlot {
-    rt::DevBuf qc, accum, meta, q0, q1, hits, sq, counts, extra, sorted, sort_table, sort_total, params;
+    rt::DevBuf qc, qr, accum, meta, q0, q1, hits, sq, counts, extra, sorted, sort_table, sort_total, params;
     rt::DevBuf depth, gbuffer, counters;
     rt::DevBuf prim_hit;   // wavefront: per pixel, sample 0's last bounce-0 hit (id, u, v) for wf_motion
     // `wf` is passed to the kernels by value and stays plain: ensure_wavefront fills it in from the

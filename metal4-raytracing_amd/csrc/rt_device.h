@@ -179,23 +179,21 @@ __host__ __device__ __forceinline__ uint32_t tri_slot(uint32_t tri_base, uint32_
     return tri_base + (uint32_t)__builtin_popcount(tri_valid & ((1u << k) - 1u));
 }
 
-// Slab-test the 8 children of a node.  Outputs: the internal children hit (bit r = internal rank r
-// = slot r), the triangles to test (nibble space: bit 4j + i = triangle i of leaf j, see
-// tri_slot), the node's tri_valid word, and the traversal direction of the slot order.
-// Branch-free over the children: each child only sets its bit of the hit-slot mask; the
-// internal / leaf split and the triangle mask follow from the node's k and tri_valid once per node.
-__host__ __device__ __forceinline__ void test_node8_words(const NodeWords& W, const RaySetup& R, float tmin, float tmax,
-                                                          uint32_t& ihits, uint32_t& tmask, uint32_t& tvalid,
-                                                          uint32_t& child_base, uint32_t& tri_base, bool& flip) {
+// Slab-test the 8 children of a node, in two parts.  node8_hit_slots: the hit-slot mask (bit c =
+// the ray reaches child slot c inside [tmin, tmax]); it reads only the slab part of the setup (ix ..
+// oz).  Branch-free over the children: each child only sets its bit.  node8_decode: what follows
+// from the mask and the node's header words (h0.w: scales, axis, k; h1) once per node: the internal
+// children hit (bit r = internal rank r = slot r), the triangles to test (nibble space: bit 4j + i
+// = triangle i of leaf j, see tri_slot), the node's tri_valid word, and the traversal direction of
+// the slot order.  test_node8_words is the two in turn.  A ray's producer may run the first part on
+// the root and hand the mask to the traversal as a root word (root_word, rt_trav.h trav_start_root).
+__host__ __device__ __forceinline__ uint32_t node8_hit_slots(const NodeWords& W, const RaySetup& R, float tmin, float tmax) {
     const float4 h0 = W.h0;
-    const NodeU3 h1 = W.h1;
     const uint4 qx = W.qx, qy = W.qy, qz = W.qz;
     const uint32_t ew = __builtin_bit_cast(uint32_t, h0.w);
     const float sx = __builtin_bit_cast(float, (ew & 0xffu) << 23);
     const float sy = __builtin_bit_cast(float, ((ew >> 8) & 0xffu) << 23);
     const float sz = __builtin_bit_cast(float, ((ew >> 16) & 0xffu) << 23);
-    const int axis = (int)((ew >> 24) & 3u);
-    const uint32_t k_int = ew >> 28;   // internal children: slots 0 .. k_int - 1
     const float ax = sx * R.ix, ay = sy * R.iy, az = sz * R.iz;
     const float bx = __builtin_fmaf(h0.x, R.ix, -R.ox);
     const float by = __builtin_fmaf(h0.y, R.iy, -R.oy);
@@ -223,13 +221,50 @@ __host__ __device__ __forceinline__ void test_node8_words(const NodeWords& W, co
         const bool hit = tn <= tf;
         hm |= hit ? (1u << c) : 0u;
     }
+    return hm;
+}
+// ew: the bits of the node's h0.w; dneg: RaySetup::dneg
+__host__ __device__ __forceinline__ void node8_decode(uint32_t hm, uint32_t ew, const NodeU3& h1, uint32_t dneg,
+                                                      uint32_t& ihits, uint32_t& tmask, uint32_t& tvalid,
+                                                      uint32_t& child_base, uint32_t& tri_base, bool& flip) {
+    const int axis = (int)((ew >> 24) & 3u);
+    const uint32_t k_int = ew >> 28;   // internal children: slots 0 .. k_int - 1
     ihits = hm & ((1u << k_int) - 1u);
     tmask = spread_nibbles(hm >> k_int) & h1.z;
     tvalid = h1.z;
     child_base = h1.x;
     tri_base = h1.y;
-    flip = (R.dneg >> axis) & 1u;   // bit select: a dynamic pick of R.d lowers to a scratch access
+    flip = (dneg >> axis) & 1u;   // bit select: a dynamic pick of R.d lowers to a scratch access
 }
+__host__ __device__ __forceinline__ void test_node8_words(const NodeWords& W, const RaySetup& R, float tmin, float tmax,
+                                                          uint32_t& ihits, uint32_t& tmask, uint32_t& tvalid,
+                                                          uint32_t& child_base, uint32_t& tri_base, bool& flip) {
+    const uint32_t hm = node8_hit_slots(W, R, tmin, tmax);
+    node8_decode(hm, __builtin_bit_cast(uint32_t, W.h0.w), W.h1, R.dneg, ihits, tmask, tvalid, child_base, tri_base, flip);
+}
+
+// ---- root word -----------------------------------------------------------------------------------
+// What a ray's producer hands its traversal about the root (node 0): kRootValid | the root's
+// hit-slot mask for the ray over [0, tmax] (tmax: infinity, or a shadow ray's).  0: not supplied,
+// the traversal tests the root itself.  RT_ROOT_MASK=0 (A/B builds): producers supply none.
+#ifndef RT_ROOT_MASK
+#define RT_ROOT_MASK 1
+#endif
+constexpr uint32_t kRootValid = 0x100u;
+__host__ __device__ __forceinline__ uint32_t root_word(const NodeWords& root, f3 o, f3 d, float tmax) {
+#if RT_ROOT_MASK
+    // the setup and the mask function the consumer would run; only the slab part of the setup is
+    // read, so its exact divisions are dead code here
+    return kRootValid | node8_hit_slots(root, ray_setup(o, d), 0.0f, tmax);
+#else
+    return 0u;
+#endif
+}
+// The root's header words as the consumer keeps them (uniform: read once per launch).
+struct RootHead {
+    uint32_t ew;
+    NodeU3 h1;
+};
 
 __host__ __device__ __forceinline__ void test_node8(const Bvh8Node* nodes, uint32_t ni, const RaySetup& R, float tmin,
                                                     float tmax, uint32_t& ihits, uint32_t& tmask, uint32_t& tvalid,

@@ -1,7 +1,7 @@
 // rt_trav.h — the stepwise traversal of the compressed 8-wide BVH: one query's state in registers
 // (Trav) and one iteration of it (trav_step), shared by wf_trace and wf_finish_step
 // (rt_wavefront.hip).  trace8 (rt_device.h) is the same traversal as a serial loop (megakernel,
-// host tools).  Device code.
+// host tools).  Host and device: tools/root_mask_check.cpp steps it on the host.
 #pragma once
 #include "rt_device.h"
 
@@ -18,7 +18,7 @@ struct Trav {
     int sp;
 };
 
-__device__ __forceinline__ void trav_start(Trav& T, f3 o, f3 d, float tmax) {
+__host__ __device__ __forceinline__ void trav_start(Trav& T, f3 o, f3 d, float tmax) {
     T.R = ray_setup(o, d);
     T.best = tmax;
     T.best_id = 0xffffffffu;
@@ -32,9 +32,22 @@ __device__ __forceinline__ void trav_start(Trav& T, f3 o, f3 d, float tmax) {
     T.hit_any = false;
 }
 
+// The start from a root word (rt_device.h): the query begins at the root's result, the state the
+// root's node step would have left (the groups, triangles and direction that node8_decode makes of
+// the producer's mask), so its first iteration is already the root's leaf triangles or first child.
+// A mask of 0 leaves nothing to do: the first trav_step returns at once (a miss / unoccluded).
+// A word of 0: the virtual root group, as trav_start.  True if the word was consumed: a counting
+// caller counts the root as one node visit.
+__host__ __device__ __forceinline__ bool trav_start_root(Trav& T, f3 o, f3 d, float tmax, uint32_t word, const RootHead& H) {
+    trav_start(T, o, d, tmax);
+    if (!(word & kRootValid)) return false;
+    node8_decode(word & 0xffu, H.ew, H.h1, T.R.dneg, T.g_hits, T.t_mask, T.t_valid, T.g_base, T.t_base, T.g_flip);
+    return true;
+}
+
 // The next node's group / stack bookkeeping and index (the step after the triangles of the last
 // node test, or a node step without triangles).
-__device__ __forceinline__ uint32_t next_node(Trav& T, int* stack, bool& overflow) {
+__host__ __device__ __forceinline__ uint32_t next_node(Trav& T, int* stack, bool& overflow) {
     if (!T.g_hits) {
         --T.sp;
         const uint32_t ent = (uint32_t)stack[T.sp * kBlock];
@@ -56,8 +69,8 @@ __device__ __forceinline__ uint32_t next_node(Trav& T, int* stack, bool& overflo
 // The node half of a traversal step: the next node of the current group (or the stack), its five
 // 16-B words from global memory, the 8-wide test.
 template <bool COUNT>
-__device__ __forceinline__ void node_step(const DevScene& S, Trav& T, int* stack, TraceCounters& tc, bool& overflow,
-                                          float cull) {
+__host__ __device__ __forceinline__ void node_step(const DevScene& S, Trav& T, int* stack, TraceCounters& tc, bool& overflow,
+                                                   float cull) {
     const uint32_t ni = next_node(T, stack, overflow);
     if (COUNT) tc.nodes++;
     const NodeWords w = load_node8(S.nodes8, ni);
@@ -75,8 +88,8 @@ __device__ __forceinline__ void node_step(const DevScene& S, Trav& T, int* stack
 // two); lower than T.best in the finish kernel's team drain (the closest hit any member of the team
 // has found), where T.best stays this lane's own hit.
 template <bool COUNT>
-__device__ __forceinline__ bool trav_step(const DevScene& S, Trav& T, bool any, int* stack, TraceCounters& tc,
-                                          bool& overflow, float cull) {
+__host__ __device__ __forceinline__ bool trav_step(const DevScene& S, Trav& T, bool any, int* stack, TraceCounters& tc,
+                                                   bool& overflow, float cull) {
     bool tdone = false;
     if (T.t_mask != 0u) {
         const int k0 = lowest_bit(T.t_mask);

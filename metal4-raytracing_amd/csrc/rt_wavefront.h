@@ -15,7 +15,7 @@ namespace rt {
 // Wavefront pipeline (rt_wavefront.hip): path state SoA indexed by path id
 // (own pixel index * spp + sample; extra samples after base_paths), ray queues of
 // {float4 o (w = path id), float4 d}, hit records {t, tri id, u, v}, shadow queue of
-// {float4 o (w = path id), float4 d (w = tmax), float4 contribution}.
+// {float4 o (w = path id), float4 d (w = tmax), float4 contribution (w = root word)}.
 struct WavefrontBuffers {
     size_t queue_entries = 0;     // kShards segments of queue_entries / kShards
     float4* p_accum = nullptr;
@@ -24,6 +24,9 @@ struct WavefrontBuffers {
     // step << 16}; qc[q][e] = the path's throughput colour (absent for state 0, the primary ray: 1)
     float4* q[2] = {nullptr, nullptr};
     float4* qc[2] = {nullptr, nullptr};
+    // qr[q][e] = the entry's root word (rt_device.h root_word): every producer writes it with the
+    // entry, 0 where it supplies none; a shadow ray's is the w of its third record
+    uint32_t* qr[2] = {nullptr, nullptr};
     float4* hits = nullptr;
     float4* sq = nullptr;
     uint32_t* counts = nullptr;   // device counter words (the map: rt_wf_counters.h)

@@ -2,16 +2,21 @@
 //
 // The per-pixel loop of raytracingKernel (Raytracing.metal:269-790) is split into stages over
 // SoA path state and compacted queues, so every wave64 works on live paths only:
-//   generate  one thread per (own pixel, sample): primary ray (:270-292) -> ray queue
-//   extend    closest-hit traversal of the ray queue (:314-322)          -> hit records
+//   generate  one thread per (own pixel, sample): primary ray (:270-292) -> ray queue, with the
+//             ray's root word (the BVH root's 8-wide test, root_word)
+//   extend    closest-hit traversal of the ray queue (:314-322)          -> hit records; a ray
+//             with a root word starts at the root's result (trav_start_root), one step later
 //   shade     shade_step per hit (:324-774): updates path state, appends the continuation
-//             ray to the next queue and the NEE shadow ray to the shadow queue; a block first
-//             compacts the hits of its queue entries, so a missed ray takes no lane
-//   connect   any-hit traversal of the shadow queue (:716-743); unoccluded -> accum += contrib
+//             ray to the next queue and the NEE shadow ray to the shadow queue, each with its
+//             root word; a block first compacts the hits of its queue entries, so a missed ray
+//             takes no lane
+//   connect   any-hit traversal of the shadow queue (:716-743); unoccluded -> accum += contrib;
+//             starts from the shadow ray's root word as extend does
 //   finish    once fewer than kTailRays paths are alive, one launch runs every remaining path
 //             to completion (trace -> shade -> shadow per thread): the long glass-path tail
 //             costs the longest remaining path instead of one launch per bounce
-//   [extra]   motion-adaptive extra samples (:779-789) as a second generate/iterate pass
+//   [extra]   motion-adaptive extra samples (:779-789) as a second generate/iterate pass (no root
+//             words: its entries carry 0 and extend tests the root itself)
 //   resolve   per pixel: sum samples in sample order, average, temporal EMA (:777, :792-819)
 //
 // Results are bit-identical to the megakernel: per-path arithmetic is the same shade_step,
@@ -92,6 +97,26 @@ __device__ __forceinline__ void write_pixel_outputs(const FrameParams& P, uint32
         P.gbuffer[2 * plane + pix] = r.g2;
         P.gbuffer[3 * plane + pix] = r.g3;
     }
+}
+
+// ---- root words (rt_device.h root_word, rt_trav.h trav_start_root) -------------------------------
+// Producers: the root's five words once per block into LDS (call before a block barrier that comes
+// before the first root_word, such as load_tabs'); the mask then costs no memory access per ray.
+__device__ __forceinline__ void stage_root(const DevScene& S, NodeWords* lds_root) {
+    static_assert(sizeof(NodeWords) == sizeof(Bvh8Node) && offsetof(NodeWords, h1) == 16 && offsetof(NodeWords, qx) == 32,
+                  "NodeWords: the node's own layout");
+    if (threadIdx.x < sizeof(Bvh8Node) / 4u)
+        reinterpret_cast<uint32_t*>(lds_root)[threadIdx.x] = reinterpret_cast<const uint32_t*>(S.nodes8)[threadIdx.x];
+}
+// Consumers: the root's header words, the same for every lane (scalar registers).
+__device__ __forceinline__ RootHead load_root_head(const DevScene& S) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(S.nodes8);
+    RootHead H;
+    H.ew = __builtin_amdgcn_readfirstlane(w[3]);
+    H.h1.x = __builtin_amdgcn_readfirstlane(w[4]);
+    H.h1.y = __builtin_amdgcn_readfirstlane(w[5]);
+    H.h1.z = __builtin_amdgcn_readfirstlane(w[6]);
+    return H;
 }
 
 }  // namespace
@@ -179,11 +204,14 @@ __global__ void __launch_bounds__(kBlock) wf_generate(DevScene S, const FramePar
     const FrameParams& P = *Pp;   // per-frame parameters in device memory
     __shared__ HaltonDim lds_halton[kHaltonLds];
     __shared__ BlockAlloc ba;
+    __shared__ NodeWords lds_root;
+    stage_root(S, &lds_root);
     const ShadeTabs halton = load_tabs(S, lds_halton, nullptr);   // no shading: Halton only
     const Uniforms& U = P.U;
     const int spp = Q.spp;
     const int shard = blockIdx.x & (kShards - 1);
     float4* qout = Q.W.q[0] + 2 * (size_t)shard * Q.seg_cap;
+    uint32_t* qrout = Q.W.qr[0] + (size_t)shard * Q.seg_cap;
     uint32_t n_paths = 0;
     const uint32_t total = Q.base_paths;
     if (Q.dev_ctl && blockIdx.x == 0 && threadIdx.x == 0) Q.W.counts[cslot(kCntFinishQ)] = (uint32_t)Q.finish_q;
@@ -203,6 +231,7 @@ __global__ void __launch_bounds__(kBlock) wf_generate(DevScene S, const FramePar
         if (live) {
             qout[2 * slot] = make_float4(o.x, o.y, o.z, __uint_as_float(pid));
             qout[2 * slot + 1] = make_float4(d.x, d.y, d.z, 0.0f);
+            qrout[slot] = root_word(lds_root, o, d, INFINITY);
         }
     }
     TraceCounters tc{0, 0, 0};
@@ -222,7 +251,9 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
     __shared__ float4 lds_inst[3 * kInstLds];
     __shared__ Light lds_light[kLightLds];
     __shared__ BlockAllocOct bao;
+    __shared__ NodeWords lds_root;
     if (tail_mode(Q)) return;
+    stage_root(S, &lds_root);
     const ShadeTabs halton = load_tabs(S, lds_halton, lds_mat, lds_inst, lds_light, P.U.lightCount);
     const Uniforms& U = P.U;
     const int next = 1 - cur;
@@ -231,6 +262,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
     const float4* qin = Q.W.q[cur];
     float4* qout = Q.W.q[next] + 2 * (size_t)shard * Q.seg_cap;
     float4* qcout = Q.W.qc[next] + (size_t)shard * Q.seg_cap;
+    uint32_t* qrout = Q.W.qr[next] + (size_t)shard * Q.seg_cap;
     float4* sqout = Q.W.sq + 3 * (size_t)shard * Q.seg_cap;
     f2 zero2;
     zero2.x = 0.0f;
@@ -371,15 +403,19 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
         const uint32_t oct = (rayD.x < 0.0f ? 1u : 0u) | (rayD.y < 0.0f ? 2u : 0u) | (rayD.z < 0.0f ? 4u : 0u);
         block_alloc3_oct(pr, oct, ctr, bao, slots);
         const uint32_t ns = slots[0], nr = front ? slots[1] : Q.seg_cap - 1u - slots[2];
+        // each ray with its root word: the root's 8-wide test here, at this kernel's lane
+        // utilisation, and the traversal starts from its result (trav_start_root)
         if (r.shadow) {
             sqout[3 * (size_t)ns] = make_float4(r.so.x, r.so.y, r.so.z, __uint_as_float(pid));
             sqout[3 * (size_t)ns + 1] = make_float4(r.sd.x, r.sd.y, r.sd.z, r.stmax);
-            sqout[3 * (size_t)ns + 2] = make_float4(r.contrib.x, r.contrib.y, r.contrib.z, 0.0f);
+            sqout[3 * (size_t)ns + 2] = make_float4(r.contrib.x, r.contrib.y, r.contrib.z,
+                                                    __uint_as_float(root_word(lds_root, r.so, r.sd, r.stmax)));
         }
         if (r.next) {
             qout[2 * (size_t)nr] = make_float4(rayO.x, rayO.y, rayO.z, __uint_as_float(pid));
             qout[2 * (size_t)nr + 1] = make_float4(rayD.x, rayD.y, rayD.z, __uint_as_float(nstate));
             qcout[nr] = ncol;
+            qrout[nr] = root_word(lds_root, rayO, rayD, INFINITY);
         }
     }
 }
@@ -552,6 +588,7 @@ wf_trace(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur, in
         Q.W.counts[cslot((ANY ? kCntChunkExtend : kCntChunkConnect) + threadIdx.x)] = 0;
     const float4* qin = ANY ? Q.W.sq : Q.W.q[cur];
     const int qstride = ANY ? 3 : 2;
+    const RootHead root = load_root_head(S);
     // chunks of this XCD's part of the queue, grabbed with one atomic per chunk
     const uint32_t xcd = blockIdx.x & 7u;
     uint32_t* const chunk_ctr = Q.W.counts + cslot((ANY ? kCntChunkConnect : kCntChunkExtend) + (int)xcd);
@@ -606,7 +643,11 @@ wf_trace(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur, in
                     e = ebase + (ANY ? g : seg_pos(g, xl, Q.seg_cap));
                     float4 o4 = qin[(size_t)qstride * e];
                     float4 d4 = qin[(size_t)qstride * e + 1];
-                    trav_start(T, ld3(o4), ld3(d4), ANY ? d4.w : INFINITY);
+                    // the entry's root word: beside a ray's entry, or in the w of a shadow ray's third record
+                    const uint32_t rw = ANY ? reinterpret_cast<const uint32_t*>(&qin[(size_t)qstride * e + 2])[3] : Q.W.qr[cur][e];
+                    // a consumed word stands for the root's node visit; a mask of 0 ends in the
+                    // lane's first trav_step below, which then does nothing (a miss / unoccluded)
+                    if (trav_start_root(T, ld3(o4), ld3(d4), ANY ? d4.w : INFINITY, rw, root) && COUNT) tc.nodes++;
                     active = true;
                     rays++;
                     if (COUNT) steps = 0;
@@ -841,7 +882,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
                     load_path(P, Q, o, d, [&]() { return ld_stream(&Q.W.qc[cur][e]); }, true, pid, meta, p);
                     rayO = ld3(o);
                     rayD = ld3(d);
-                    trav_start(T, rayO, rayD, INFINITY);
+                    trav_start(T, rayO, rayD, INFINITY);   // the entry's root word (qr) is not read: no register for it here
                     mode = kClosest;
                     n_closest++;
                     segs++;
@@ -1084,6 +1125,7 @@ __global__ void __launch_bounds__(kBlock) wf_extra(DevScene S, const FrameParams
     const int stride = Q.spp + maxExtra;
     const int shard = blockIdx.x & (kShards - 1);
     float4* qout = Q.W.q[qidx] + 2 * (size_t)shard * Q.seg_cap;
+    uint32_t* qrout = Q.W.qr[qidx] + (size_t)shard * Q.seg_cap;
     __shared__ BlockAlloc ba;
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     int px = 0, py = 0, e = 0;
@@ -1117,6 +1159,7 @@ __global__ void __launch_bounds__(kBlock) wf_extra(DevScene S, const FrameParams
                 const uint32_t slot = slot0 + (uint32_t)j;
                 qout[2 * (size_t)slot] = make_float4(o.x, o.y, o.z, __uint_as_float(pid));
                 qout[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, 0.0f);
+                qrout[slot] = 0u;   // no root word: extend tests the root itself (few rays, and not every frame)
             }
         }
     }

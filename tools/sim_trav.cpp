@@ -58,6 +58,10 @@ struct Policy {
     int coop = 0;           // > 0: the wave tests every pending triangle of the tri-phase lanes in batches of 64
                             // (one per lane, owner's ray via LDS / bpermute); coop = per-batch overhead issues
     int pairs = 0;          // 1: edge-sharing pairs of a leaf (Bvh8Node::reserved) tested as one pair step
+    int root_known = 0;     // 1: the ray arrives with the root's test done by its producer (root word,
+                            // rt_trav.h trav_start_root): its first step is the root's triangles or first
+                            // child.  The producer's cost is not in this model (wf_shade / wf_generate run
+                            // the same ~194-issue test at their own, higher lane utilisation).
 };
 
 struct Scene8 {
@@ -65,7 +69,7 @@ struct Scene8 {
     std::vector<float4> tris;   // 3 per slot
 };
 
-static void start(Lane& L, const Ray& r) {
+static void start(Lane& L, const Ray& r, const Bvh8Node* nodes = nullptr, bool root_known = false) {
     L.R = ray_setup(r.o, r.d);
     L.o = r.o;
     L.best = INFINITY;
@@ -79,6 +83,10 @@ static void start(Lane& L, const Ray& r) {
     L.sp = 0;
     L.active = true;
     L.steps = 0;
+    if (root_known) {   // the state the root's node step leaves; a ray that misses the root ends in its first step
+        test_node8(nodes, 0u, L.R, 0.0f, L.best, L.g_hits, L.t_mask, L.t_valid, L.g_base, L.t_base, L.g_flip);
+        L.t_pair = nodes[0].reserved;
+    }
 }
 
 // Edge-sharing triangle pairs inside the leaves (DESIGN.md §3.1 "Triangle pairs").  Two triangles
@@ -224,7 +232,7 @@ static Result simulate(const Scene8& S, const std::vector<Ray>& rays, const Poli
                 int got = 0;
                 for (auto& L : lanes)
                     if (!L.active && wnext[w] < wend[w]) {
-                        start(L, rays[wnext[w]]);
+                        start(L, rays[wnext[w]], S.nodes.data(), P.root_known != 0);
                         L.ray = (int)wnext[w];
                         ++wnext[w];
                         ++got;
@@ -431,6 +439,7 @@ int main(int argc, char** argv) {
     std::vector<Policy> pols;
     pols.push_back(Policy{"current (refill 8, 2 tris)", 8, 2, 0});
     if (getenv("SIM_PAIRS")) pols.push_back(Policy{"edge-sharing pairs", 8, 2, 0, 0, 0, 1});
+    pols.push_back(Policy{"root known (root word)", 8, 2, 0, 0, 0, 0, 1});
     pols.push_back(Policy{"refill 16", 16, 2, 0});
     pols.push_back(Policy{"1 tri per step", 8, 1, 0});
     pols.push_back(Policy{"4 tris per step", 8, 4, 0});
