@@ -534,7 +534,9 @@ typedef struct rt_path {          /* 48 B, three 16-B words, 16-byte aligned */
     float    radiance[3];         /* the renderer's `accum` */
     uint32_t flags;               /* RT_PATH_* */
     int32_t  bounce, step, transparency_passes;
-    uint32_t reserved;            /* 0 */
+    uint32_t reserved;            /* the record's tag: rt_shade_hits carries this word through unchanged;
+                                     rt_camera_paths sets it, rt_retire_paths scatters by it (path
+                                     queries, below); 0 where the caller has no use for it */
 } rt_path;
 #define RT_PATH_ALIVE  1u   /* in: shade this record; out: trace next_rays[i] again */
 #define RT_PATH_SHADOW 2u   /* out: shadow_rays[i] / contrib[i] are live for this step */
@@ -599,6 +601,102 @@ rt_status rt_shade_hits_on(rt_ctx* ctx, const rt_shade_opts* opts, const rt_ray*
                            const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths,
                            rt_ray* next_rays, rt_ray* shadow_rays, float* contrib, void* hip_stream);
 
+/* ---- Path queries: camera rays, stable compaction, connect, retire, average ----------------------
+ * What a caller's loop does between the queries above, so that the whole integrator runs from
+ * library calls (no framework glue, no host arithmetic):
+ *   rt_camera_paths -> { rt_trace_closest -> rt_resolve_hits -> rt_shade_hits
+ *                        -> rt_compact_paths(RT_PATH_SHADOW: shadow rays + index) -> rt_trace_any
+ *                        -> rt_connect_paths -> rt_retire_paths
+ *                        -> rt_compact_paths(RT_PATH_ALIVE: next rays + paths) } until count == 0
+ *   -> rt_average_samples
+ * equals rt_render_frame's radiance of frame 0 bit for bit, all four channels.  The host's only
+ * part per round is reading the 4-byte count of each compaction (the `n` of the next launches).
+ *
+ * All data pointers are DEVICE pointers.  Every call follows rt_resolve_hits' conventions: it
+ * enqueues launches only (no host wait, no allocation in the steady state); the plain form runs
+ * on the context's stream, the _on form on `hip_stream` exactly as given; each call takes one of
+ * the ring of query slots, so back-to-back calls on different streams need no host wait;
+ * rt_wait, rt_destroy and geometry updates wait for it; it is not folded into rt_query_stats;
+ * n == 0 returns RT_OK with nothing launched (and nothing written); a NULL or misaligned pointer
+ * is RT_ERR_INVALID_ARG on the host before any launch.  Record arrays are 16-byte aligned,
+ * uint32_t arrays 4-byte aligned.  Frames rendered with these calls interleaved are bit-identical
+ * to frames rendered without.  None of them needs a scene or a BVH. */
+typedef struct rt_camera_opts {   /* 32 B */
+    uint32_t first_pixel;         /* record i is pixel first_pixel + i, row-major */
+    int32_t  sample;              /* sample number within the pixel, >= 0 */
+    uint32_t tag_stride;          /* tag = pixel * tag_stride + tag_offset; >= 1 */
+    uint32_t tag_offset;
+    uint32_t reserved[4];
+} rt_camera_opts;
+RT_STATIC_ASSERT(sizeof(rt_camera_opts) == 32, "rt_camera_opts is 32 B");
+
+typedef struct rt_compact_stream { /* 24 B */
+    const void* src;
+    void*       dst;
+    uint32_t    words;            /* 16-B words per record, 1..4: 1 contrib; 2 rays, hits; 3 paths,
+                                     materials; 4 surfaces */
+    uint32_t    _pad;
+} rt_compact_stream;
+RT_STATIC_ASSERT(sizeof(rt_compact_stream) == 24, "rt_compact_stream is 24 B");
+
+/* rt_camera_paths: the renderer's primary rays and path states.  Record i is pixel pix =
+ * first_pixel + i (px = pix % width, py = pix / width of u->width x u->height).  Its Halton index
+ * is the renderer's: random[pix] + frameIndex * (samplesPerPixel + maxExtra) + sample in uint32
+ * arithmetic, maxExtra = enableMotionAdaptiveSampling ? max(motionSamplingMaxExtraSamples, 0) : 0.
+ * rays[i] is the renderer's primary ray of that index (origin word 3 = 0, tmax = INFINITY);
+ * paths[i] is throughput 1, `sample` = the Halton index, radiance 0, flags RT_PATH_ALIVE, bounce =
+ * step = transparency_passes = 0, tag (`reserved`) = pix * tag_stride + tag_offset.
+ * random_offsets: a device array of width * height words, or NULL = the context's own from
+ * rt_resize (RT_ERR_STATE without one, or when its size is not u->width x u->height).
+ * RT_ERR_INVALID_ARG: first_pixel + n > width * height, a non-positive size, sample < 0,
+ * tag_stride == 0.  Reads no scene and no BVH. */
+rt_status rt_camera_paths(rt_ctx* ctx, const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
+                          uint32_t n, rt_ray* rays, rt_path* paths);
+rt_status rt_camera_paths_on(rt_ctx* ctx, const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
+                             uint32_t n, rt_ray* rays, rt_path* paths, void* hip_stream);
+
+/* rt_compact_paths: stable stream compaction by path flags.  The selected set is every i < n with
+ * (paths[i].flags & mask) != 0, m of them.  For the j-th selected record in ascending i:
+ * dst_k[j] = src_k[i] for each of the stream_count (0..4) streams, as whole 16-B words;
+ * index[j] = i unless index is NULL; *count = m.  Nothing is written at or beyond m.  The result
+ * is what a[(flags & mask) != 0] gives in numpy: stable, deterministic, identical from call to
+ * call.  Three launches: per-tile counts and a selection bitmask, a one-block scan of the tile
+ * counts, per-tile rank and copy; no block waits for another.  Temporary storage (132 B per 1024
+ * records) belongs to the call's query slot, grows on demand and is counted in
+ * rt_stats.device_bytes.
+ * `paths` may itself be a src.  NOT in place: no dst (nor index, nor count) may overlap any src,
+ * any other dst or paths; the call can only check that the base pointers differ.
+ * RT_ERR_INVALID_ARG: mask == 0, stream_count > 4, words outside 1..4, equal base pointers. */
+rt_status rt_compact_paths(rt_ctx* ctx, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
+                           uint32_t stream_count, uint32_t* index, uint32_t* count);
+rt_status rt_compact_paths_on(rt_ctx* ctx, const rt_path* paths, uint32_t n, uint32_t mask,
+                              const rt_compact_stream* streams, uint32_t stream_count, uint32_t* index, uint32_t* count,
+                              void* hip_stream);
+
+/* rt_connect_paths: applies traced shadow rays.  For j < m with occluded[j] == 0 and
+ * i = index ? index[j] : j: paths[i].radiance += contrib[i].rgb (contrib: four floats per record,
+ * as rt_shade_hits writes them; three fp32 adds, the renderer's accum = accum + contrib); nothing
+ * else in the record changes.  An i >= n is skipped and never dereferenced.  The index entries
+ * must be distinct (rt_compact_paths' are): otherwise two threads update one record. */
+rt_status rt_connect_paths(rt_ctx* ctx, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                           const uint32_t* occluded, uint32_t m);
+rt_status rt_connect_paths_on(rt_ctx* ctx, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                              const uint32_t* occluded, uint32_t m, void* hip_stream);
+
+/* rt_retire_paths: for every record with RT_PATH_ALIVE clear and tag < tags,
+ * samples[tag] = (radiance.r, radiance.g, radiance.b, 1.0f), one 16-B store.  A pure scatter: with
+ * distinct tags the result does not depend on order.  A tag at or above `tags` is skipped. */
+rt_status rt_retire_paths(rt_ctx* ctx, const rt_path* paths, uint32_t n, float* samples, uint32_t tags);
+rt_status rt_retire_paths_on(rt_ctx* ctx, const rt_path* paths, uint32_t n, float* samples, uint32_t tags,
+                             void* hip_stream);
+
+/* rt_average_samples: rgba[p].rgb = (((s[p*spp] + s[p*spp+1]) + ...) + s[p*spp+spp-1]) / (float)spp
+ * in fp32, in sample order (the renderer's resolve of frame 0); alpha = 1.0f as the renderer stores
+ * it.  spp is 1..64.  No EMA, no motion, no G-buffer. */
+rt_status rt_average_samples(rt_ctx* ctx, const float* samples, uint32_t pixels, uint32_t spp, float* rgba);
+rt_status rt_average_samples_on(rt_ctx* ctx, const float* samples, uint32_t pixels, uint32_t spp, float* rgba,
+                                void* hip_stream);
+
 /* Library build identification (kernel code object arch etc). */
 const char* rt_version(void);
 
@@ -624,6 +722,17 @@ rt_status rt_debug_resolve_host(const rt_scene_desc* scene, const rt_ray* rays, 
 rt_status rt_debug_shade_host(const Light* lights, uint32_t light_count, const rt_shade_opts* opts, const rt_ray* rays,
                               const rt_surface* surfaces, const rt_surface_material* materials, const float* randoms,
                               uint32_t n, rt_path* paths, rt_ray* next_rays, rt_ray* shadow_rays, float* contrib);
+
+/* Test hook (host only, no device): rt_camera_paths over host arrays, by the code the kernel runs,
+ * compiled for the host.  All pointers are HOST pointers; random_offsets is required (width *
+ * height words); the same checks. */
+rt_status rt_debug_camera_paths_host(const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
+                                     uint32_t n, rt_ray* rays, rt_path* paths);
+
+/* Test hook (host only, no device): rt_compact_paths over host arrays, a sequential loop; the same
+ * checks. */
+rt_status rt_debug_compact_paths_host(const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
+                                      uint32_t stream_count, uint32_t* index, uint32_t* count);
 
 #ifdef __cplusplus
 }

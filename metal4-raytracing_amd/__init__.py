@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (TEXTURE_SLOTS, Tuning, Camera, Float3, Light, MaterialOverride, PackedFloat4x3, SceneDesc, Stats, TextureDesc,
-                   TileSet, Uniforms, Ray, RayHit, QueryStats, Path, ShadeOpts,
+                   TileSet, Uniforms, Ray, RayHit, QueryStats, Path, ShadeOpts, CameraOpts, CompactStream,
                    f3)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -171,6 +171,28 @@ def debug_shade_host(lights, rays, surface, paths, randoms=None, shading_mode=0,
                                      rnd.ctypes.data if rnd is not None else None, n, p.ctypes.data, nxt.ctypes.data,
                                      sh.ctypes.data, con.ctypes.data))
     return Shaded(Paths(p, p.view(np.int32)), nxt, sh, con)
+
+
+def _camera_opts(sample, first_pixel, tag_stride, tag_offset):
+    o = CameraOpts()
+    o.first_pixel, o.sample, o.tag_stride, o.tag_offset = int(first_pixel), int(sample), int(tag_stride), int(tag_offset)
+    return o
+
+
+def debug_camera_paths_host(uniforms, random_offsets, sample, first_pixel=0, n=None, tag_stride=1, tag_offset=0):
+    """Test hook: rt_camera_paths on the host (rt_debug_camera_paths_host).  random_offsets: the
+    width * height uint32 offsets (random_offsets()).  Returns ((n, 8) float32 rays, Paths) as
+    numpy arrays; n defaults to the pixels from first_pixel on."""
+    rnd = np.ascontiguousarray(random_offsets, np.uint32).reshape(-1)
+    if n is None:
+        n = max(uniforms.width * uniforms.height - first_pixel, 0)
+    if rnd.shape[0] != uniforms.width * uniforms.height:
+        raise ValueError(f"random_offsets must hold {uniforms.width * uniforms.height} words, not {rnd.shape[0]}")
+    rays, p = np.empty((n, 8), np.float32), np.empty((n, 12), np.float32)
+    o = _camera_opts(sample, first_pixel, tag_stride, tag_offset)
+    _check(lib().rt_debug_camera_paths_host(C.byref(uniforms), C.byref(o), rnd.ctypes.data, n, rays.ctypes.data,
+                                            p.ctypes.data))
+    return rays, Paths(p, p.view(np.int32))
 
 
 def glass_override():
@@ -399,6 +421,7 @@ class Paths:
         self.throughput, self.radiance = buffer[:, 0:3], buffer[:, 4:7]
         self.sample, self.flags = as_int[:, 3], as_int[:, 7]
         self.bounce, self.step, self.transparency_passes = as_int[:, 8], as_int[:, 9], as_int[:, 10]
+        self.tag = as_int[:, 11]   # rt_path.reserved: carried through by shade, set by camera_paths, read by retire
 
     def __len__(self):
         return self.buffer.shape[0]
@@ -422,6 +445,21 @@ class Shaded:
 
     def __len__(self):
         return len(self.paths)
+
+
+class Compacted:
+    """Results of Renderer.compact: `count` (a 1-element int32 tensor: the number selected),
+    `index` (int32, the selected records' positions in ascending order; None when not asked for)
+    and `outs` (one full-length tensor per stream; the first `count` records of each are the
+    selected ones, the rest is untouched).  n() reads the count back, ordered after the compaction
+    on the stream it ran on; slice the tensors with it."""
+
+    def __init__(self, count, index, outs, host, sync):
+        self.count, self.index, self.outs = count, index, outs
+        self._host, self._sync = host, sync
+
+    def n(self):
+        return self._sync(self)
 
 
 def _shade_opts(shading_mode, max_bounces, light_count):
@@ -756,6 +794,275 @@ class Renderer:
             pn = p.cpu().numpy()
             return Shaded(Paths(pn, pn.view(np.int32)), *(x.cpu().numpy() for x in outs))
         return Shaded(paths if isinstance(paths, Paths) else Paths(p, p.view(torch.int32)), *outs)
+
+    # --- path queries: the glue of a query integrator as library calls ---
+    def _records(self, x, name, cols=None, rows=None, dtypes=None):
+        """A contiguous 2-D tensor of 4-byte elements on the renderer's device (cols: an int or the
+        allowed widths), or ValueError."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        dtypes = dtypes or (torch.float32,)
+        cols_ok = (cols,) if isinstance(cols, int) else cols
+        if (not isinstance(x, torch.Tensor) or x.dtype not in dtypes or x.dim() != 2 or not x.is_contiguous()
+                or x.device != dev or (cols_ok is not None and x.shape[1] not in cols_ok)
+                or (rows is not None and x.shape[0] != rows)):
+            raise ValueError(f"{name} must be a contiguous {' / '.join(str(d) for d in dtypes)} "
+                             f"({'n' if rows is None else rows}, {cols}) tensor on {dev}")
+        return x
+
+    def _words(self, x, name, rows=None):
+        """A contiguous int32 vector on the renderer's device, or ValueError."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(x, torch.Tensor) or x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous()
+                or x.device != dev or (rows is not None and x.shape[0] != rows)):
+            raise ValueError(f"{name} must be a contiguous int32 ({'n' if rows is None else rows},) tensor on {dev}")
+        return x
+
+    def _torch_stream(self, stream):
+        """The torch stream of a HIP stream handle (0 = torch's default stream)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        return torch.cuda.default_stream(dev) if not stream else torch.cuda.ExternalStream(stream, device=dev)
+
+    def camera_paths(self, sample, first_pixel=0, n=None, uniforms=None, random_offsets=None, tag_stride=1, tag_offset=0,
+                     out=None, stream=None):
+        """rt_camera_paths: the renderer's primary rays and path states of sample `sample` for the n
+        pixels from first_pixel on (row-major; default: the rest of the image), by the given
+        uniforms (default: the Renderer's current ones: camera, size, frameIndex, samplesPerPixel).
+        random_offsets: None = the renderer's own, or width * height offsets as an int32 tensor on
+        the device (a host array is staged).  Each path's tag is pixel * tag_stride + tag_offset.
+        `out` is a pair of float32 tensors ((n, 8) rays, (n, 12) paths).  Enqueued on `stream` (as
+        in trace) without a host wait.  Returns (rays, Paths)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        u = uniforms if uniforms is not None else self.uniforms()
+        if n is None:
+            n = u.width * u.height - int(first_pixel)
+        if n < 0:
+            raise ValueError("first_pixel is past the image")
+        rnd = random_offsets
+        if rnd is not None:
+            if not isinstance(rnd, torch.Tensor):
+                rnd = torch.from_numpy(np.ascontiguousarray(rnd, np.uint32).reshape(-1).view(np.int32)).to(dev)
+                torch.cuda.current_stream(dev).synchronize()   # the staging copy
+            self._words(rnd, "random_offsets", u.width * u.height)
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError("out must be (rays, paths)")
+        rays = self._records(out[0], "out rays", 8, n) if out is not None else torch.empty((n, 8), dtype=torch.float32, device=dev)
+        pb = self._records(out[1], "out paths", 12, n) if out is not None else torch.empty((n, 12), dtype=torch.float32, device=dev)
+        o = _camera_opts(sample, first_pixel, tag_stride, tag_offset)
+        vp = C.c_void_p
+        args = (self._ctx, C.byref(u), C.byref(o), vp(rnd.data_ptr()) if rnd is not None else None, n, vp(rays.data_ptr()),
+                vp(pb.data_ptr()))
+        if stream is None:
+            _check(lib().rt_camera_paths(*args), self._ctx)
+        else:
+            _check(lib().rt_camera_paths_on(*args, vp(stream)), self._ctx)
+        return rays, Paths(pb, pb.view(torch.int32))
+
+    def compact(self, paths, mask, streams=(), index=True, out=None, stream=None):
+        """rt_compact_paths: stable compaction of up to four record streams by the paths' flags:
+        the records i with paths.flags[i] & mask != 0, in ascending i, what x[(flags & mask) != 0]
+        gives.  `paths` is a Paths or its (n, 12) buffer; `streams` are (n, 4 * words) tensors of
+        4-byte elements, words 1 .. 4 (the paths buffer itself may be one).  index: True = also
+        return the selected positions, False = not, or an int32 (n,) tensor to write them to.
+        out: a Compacted of an earlier call of the same shapes, or a tuple (outs, index, count) of
+        tensors to write to (outs: one per stream, same shape and type; index / count may be None).
+        Not in place: no output may be an input.  Enqueued on `stream` (as in trace) without a
+        host wait; Compacted.n() reads the count back."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        four = (torch.float32, torch.int32)
+        pb = self._records(paths.buffer if isinstance(paths, Paths) else paths, "paths", 12)
+        n = pb.shape[0]
+        srcs = [self._records(x, f"stream {k}", (4, 8, 12, 16), n, four) for k, x in enumerate(streams)]
+        if len(srcs) > 4:
+            raise ValueError("at most four streams")
+        o_outs = o_index = o_count = host = None
+        if isinstance(out, Compacted):
+            o_outs, o_index, o_count, host = out.outs, out.index, out.count, out._host
+        elif out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("out must be a Compacted or (outs, index, count)")
+            o_outs, o_index, o_count = out
+        if o_outs is not None and len(o_outs) != len(srcs):
+            raise ValueError(f"{len(srcs)} streams but {len(o_outs)} out tensors")
+        outs = []
+        for k, x in enumerate(srcs):
+            d = o_outs[k] if o_outs is not None else torch.empty_like(x)
+            self._records(d, f"out {k}", x.shape[1], n, (x.dtype,))
+            outs.append(d)
+        if isinstance(index, torch.Tensor):
+            idx = self._words(index, "index", n)
+        elif index:
+            idx = self._words(o_index, "out index", n) if o_index is not None else torch.empty((n,), dtype=torch.int32, device=dev)
+        else:
+            idx = None
+        count = self._words(o_count, "out count", 1) if o_count is not None else torch.empty((1,), dtype=torch.int32, device=dev)
+        if host is None:
+            host = torch.empty((1,), dtype=torch.int32, pin_memory=True)
+        arr = (CompactStream * max(len(srcs), 1))()
+        for k, (x, d) in enumerate(zip(srcs, outs)):
+            arr[k].src, arr[k].dst, arr[k].words = x.data_ptr(), d.data_ptr(), x.shape[1] // 4
+        vp = C.c_void_p
+        if n == 0:   # nothing is launched and nothing written: the count is ours to set
+            with torch.cuda.stream(self._torch_stream(stream) if stream is not None else torch.cuda.current_stream(dev)):
+                count.zero_()
+        args = (self._ctx, vp(pb.data_ptr()), n, int(mask), arr, len(srcs), vp(idx.data_ptr()) if idx is not None else None,
+                vp(count.data_ptr()))
+        if stream is None:
+            _check(lib().rt_compact_paths(*args), self._ctx)
+        else:
+            _check(lib().rt_compact_paths_on(*args, vp(stream)), self._ctx)
+
+        def sync(cp, stream=stream):
+            if stream is None:
+                self.wait()   # the renderer's own stream is not torch's to name
+                cp._host.copy_(cp.count)
+            else:
+                ts = self._torch_stream(stream)
+                with torch.cuda.stream(ts):
+                    cp._host.copy_(cp.count, non_blocking=True)
+                ts.synchronize()
+            return int(cp._host[0])
+
+        return Compacted(count, idx, outs, host, sync)
+
+    def connect(self, paths, contrib, occluded, index=None, m=None, stream=None):
+        """rt_connect_paths: paths.radiance[i] += contrib[i] for the first m shadow rays j that
+        are not occluded (occluded[j] == 0), i = index[j] (or j without an index).  `paths`
+        (Paths or buffer) is updated IN PLACE; contrib is (n, 4) float32, occluded and index int32
+        vectors of at least m entries (m defaults to len(occluded)).  The index entries must be
+        distinct, as compact() makes them.  Enqueued on `stream` without a host wait."""
+        pb = self._records(paths.buffer if isinstance(paths, Paths) else paths, "paths", 12)
+        n = pb.shape[0]
+        con = self._records(contrib, "contrib", 4, n)
+        occ = self._words(occluded, "occluded")
+        idx = self._words(index, "index") if index is not None else None
+        m = occ.shape[0] if m is None else int(m)
+        if m < 0 or m > occ.shape[0] or (idx is not None and m > idx.shape[0]):
+            raise ValueError(f"m = {m} is more than occluded / index hold")
+        vp = C.c_void_p
+        args = (self._ctx, vp(pb.data_ptr()), n, vp(con.data_ptr()), vp(idx.data_ptr()) if idx is not None else None,
+                vp(occ.data_ptr()), m)
+        if stream is None:
+            _check(lib().rt_connect_paths(*args), self._ctx)
+        else:
+            _check(lib().rt_connect_paths_on(*args, vp(stream)), self._ctx)
+
+    def retire(self, paths, samples, stream=None):
+        """rt_retire_paths: samples[tag] = (radiance, 1) for every path that is not ALIVE and whose
+        tag is below len(samples); `samples` is a (tags, 4) float32 tensor.  Enqueued on `stream`
+        without a host wait."""
+        pb = self._records(paths.buffer if isinstance(paths, Paths) else paths, "paths", 12)
+        sm = self._records(samples, "samples", 4)
+        vp = C.c_void_p
+        args = (self._ctx, vp(pb.data_ptr()), pb.shape[0], vp(sm.data_ptr()), sm.shape[0])
+        if stream is None:
+            _check(lib().rt_retire_paths(*args), self._ctx)
+        else:
+            _check(lib().rt_retire_paths_on(*args, vp(stream)), self._ctx)
+
+    def average(self, samples, spp, out=None, stream=None):
+        """rt_average_samples: (pixels * spp, 4) float32 samples, a pixel's spp samples side by
+        side, into (pixels, 4): their sum in sample order / spp, alpha 1, as the renderer resolves
+        frame 0.  Enqueued on `stream` without a host wait.  Returns the (pixels, 4) tensor."""
+        import torch
+        sm = self._records(samples, "samples", 4)
+        spp = int(spp)
+        if spp < 1 or sm.shape[0] % spp:
+            raise ValueError(f"{sm.shape[0]} samples are not a multiple of spp = {spp}")
+        pixels = sm.shape[0] // spp
+        if out is None:
+            out = torch.empty((pixels, 4), dtype=torch.float32, device=sm.device)
+        self._records(out, "out", 4, pixels)
+        vp = C.c_void_p
+        args = (self._ctx, vp(sm.data_ptr()), pixels, spp, vp(out.data_ptr()))
+        if stream is None:
+            _check(lib().rt_average_samples(*args), self._ctx)
+        else:
+            _check(lib().rt_average_samples_on(*args, vp(stream)), self._ctx)
+        return out
+
+    def _path_buffers(self, cap, tags):
+        """path_trace's working set, allocated once per size: two sets of rays and paths to
+        ping-pong between, one of everything else."""
+        import torch
+        have = self.__dict__.get("_pt_buffers")
+        if have is not None and have["cap"] == cap and have["tags"] == tags:
+            return have
+        dev = torch.device("cuda", self.device)
+        f = lambda cols, rows=cap: torch.empty((rows, cols), dtype=torch.float32, device=dev)
+        w = lambda rows=cap: torch.empty((rows,), dtype=torch.int32, device=dev)
+        pin = lambda: torch.empty((1,), dtype=torch.int32, pin_memory=True)
+        b = dict(cap=cap, tags=tags, rays=[f(8), f(8)], paths=[f(12), f(12)], hits=f(8), surf=f(16), mat=f(12), nxt=f(8),
+                 shadow=f(8), contrib=f(4), shadow_c=f(8), sh_index=w(), occluded=w(), samples=f(4, tags),
+                 counts=[w(1), w(1)], pinned=[pin(), pin()])
+        self._pt_buffers = b
+        return b
+
+    def path_trace(self, spp=None, max_bounces=None, shading_mode=None, stream=0, batch_samples=True):
+        """Frame 0 of the current uniforms from queries only: camera_paths, then per round
+        trace -> resolve -> shade -> compact(SHADOW: shadow rays + index) -> trace(any_hit) ->
+        connect -> retire -> compact(ALIVE: next rays + paths) until no path is left, then
+        average.  Bit-identical to draw() + radiance() of frame 0 in all four channels.  The host's
+        part per round is reading the two compactions' counts.  batch_samples: all samples of the
+        image in one array (tag = pixel * spp + s), else one sample at a time.  Runs on `stream`
+        (as in trace; default 0 = torch's default stream); the working buffers are allocated once
+        per size and kept.  Returns the (H, W, 4) float32 tensor, valid on that stream; the ray
+        totals are kept in `last_path_trace` (closest_rays, shadow_rays, paths, rounds)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        spp = int(self.samplesPerPixel if spp is None else spp)
+        mb = int(self.maxBounces if max_bounces is None else max_bounces)
+        mode = int(self.shadingMode if shading_mode is None else shading_mode)
+        if spp < 1 or spp > 64:
+            raise ValueError("spp outside 1 .. 64")
+        u = self.uniforms()
+        u.frameIndex, u.samplesPerPixel = 0, spp
+        pixels = self.width * self.height
+        guard = mb * (mb + 1) + 1   # shade steps a path can take at most (tests/shade_ref.py guard_steps)
+        ts = self._torch_stream(stream) if stream is not None else None
+        with torch.cuda.stream(ts if ts is not None else torch.cuda.current_stream(dev)):
+            B = self._path_buffers(pixels * spp if batch_samples else pixels, pixels * spp)
+            image = torch.empty((pixels, 4), dtype=torch.float32, device=dev)
+        A, SH = Paths.ALIVE, Paths.SHADOW
+        q = dict(stream=stream)
+        totals = dict(closest_rays=0, shadow_rays=0, paths=pixels * spp, rounds=0)
+        for group in ([range(spp)] if batch_samples else [[s] for s in range(spp)]):
+            cur = 0
+            for s in group:
+                k = s * pixels if batch_samples else 0
+                self.camera_paths(s, uniforms=u, tag_stride=spp, tag_offset=s,
+                                  out=(B["rays"][cur][k:k + pixels], B["paths"][cur][k:k + pixels]), **q)
+            n, rounds = B["cap"], 0
+            while n > 0:
+                if rounds >= guard:
+                    raise RuntimeError(f"a path outlived the renderer's longest ({guard} steps)")
+                rays, pb = B["rays"][cur][:n], B["paths"][cur][:n]
+                nxt, shadow, contrib = B["nxt"][:n], B["shadow"][:n], B["contrib"][:n]
+                hits = self.trace(rays, out=B["hits"][:n], **q)
+                S = self.resolve(rays, hits, out=(B["surf"][:n], B["mat"][:n]), **q)
+                self.shade(rays, S, pb, shading_mode=mode, max_bounces=mb, out=(nxt, shadow, contrib), **q)
+                ns = self.compact(pb, SH, (shadow,), out=Compacted(B["counts"][0], B["sh_index"][:n], [B["shadow_c"][:n]],
+                                                                    B["pinned"][0], None), **q).n()
+                if ns:
+                    self.trace(B["shadow_c"][:ns], any_hit=True, out=B["occluded"][:ns], **q)
+                    self.connect(pb, contrib, B["occluded"][:ns], index=B["sh_index"][:ns], m=ns, **q)
+                self.retire(pb, B["samples"], **q)
+                na = self.compact(pb, A, (nxt, pb), index=False,
+                                  out=Compacted(B["counts"][1], None, [B["rays"][1 - cur][:n], B["paths"][1 - cur][:n]],
+                                                B["pinned"][1], None), **q).n()
+                totals["closest_rays"] += n
+                totals["shadow_rays"] += ns
+                n, cur, rounds = na, 1 - cur, rounds + 1
+            totals["rounds"] = max(totals["rounds"], rounds)
+        self.average(B["samples"], spp, out=image, **q)
+        if stream is None:
+            self.wait()
+        self.last_path_trace = totals
+        return image.view(self.height, self.width, 4)
 
     def query_stats(self):
         """rt_get_query_stats (waits for pending queries): the last query and the running totals."""

@@ -224,7 +224,8 @@ RT_SURFACE_HAS_UV, RT_SURFACE_BACKFACE, RT_SURFACE_NORMAL_MAPPED, RT_SURFACE_TRA
 
 class Path(C.Structure):  # rt_path: 48 B, three 16-B words
     _fields_ = [("throughput", C.c_float * 3), ("sample", C.c_uint32), ("radiance", C.c_float * 3), ("flags", C.c_uint32),
-                ("bounce", C.c_int32), ("step", C.c_int32), ("transparency_passes", C.c_int32), ("reserved", C.c_uint32)]
+                ("bounce", C.c_int32), ("step", C.c_int32), ("transparency_passes", C.c_int32),
+                ("reserved", C.c_uint32)]   # the record's tag: rt_shade_hits carries it through (path queries)
 
 
 RT_PATH_ALIVE, RT_PATH_SHADOW = 1, 2
@@ -233,6 +234,15 @@ RT_PATH_ALIVE, RT_PATH_SHADOW = 1, 2
 class ShadeOpts(C.Structure):  # rt_shade_opts: 32 B
     _fields_ = [("shading_mode", C.c_int32), ("max_bounces", C.c_int32), ("light_count", C.c_int32),
                 ("reserved", C.c_int32 * 5)]
+
+
+class CameraOpts(C.Structure):  # rt_camera_opts: 32 B
+    _fields_ = [("first_pixel", C.c_uint32), ("sample", C.c_int32), ("tag_stride", C.c_uint32), ("tag_offset", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class CompactStream(C.Structure):  # rt_compact_stream: 24 B
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("words", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class QueryStats(C.Structure):  # rt_query_stats
@@ -301,7 +311,10 @@ EXPORTED_SYMBOLS = [
     "rt_set_counting", "rt_set_device_spans", "rt_set_graphs", "rt_get_stats", "rt_set_tuning", "rt_get_tuning",
     "rt_trace_closest", "rt_trace_any", "rt_trace_closest_on", "rt_trace_any_on", "rt_get_query_stats",
     "rt_resolve_hits", "rt_resolve_hits_on", "rt_shade_hits", "rt_shade_hits_on",
+    "rt_camera_paths", "rt_camera_paths_on", "rt_compact_paths", "rt_compact_paths_on", "rt_connect_paths",
+    "rt_connect_paths_on", "rt_retire_paths", "rt_retire_paths_on", "rt_average_samples", "rt_average_samples_on",
     "rt_version", "rt_debug_trace_host", "rt_debug_resolve_host", "rt_debug_shade_host",
+    "rt_debug_camera_paths_host", "rt_debug_compact_paths_host",
     # rt_scene.h
     "rt_material_override_glass", "rt_scene_new", "rt_scene_free", "rt_scene_last_error",
     "rt_scene_add_obj", "rt_scene_add_usd", "rt_scene_add_procedural", "rt_scene_set_lights", "rt_scene_set_light_intensity",
@@ -363,6 +376,18 @@ def declare(lib):
         "rt_shade_hits": (st, [vp, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
         "rt_shade_hits_on": (st, [vp, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
         "rt_debug_shade_host": (st, [P(Light), C.c_uint32, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+        "rt_camera_paths": (st, [vp, P(Uniforms), P(CameraOpts), vp, C.c_uint32, vp, vp]),
+        "rt_camera_paths_on": (st, [vp, P(Uniforms), P(CameraOpts), vp, C.c_uint32, vp, vp, vp]),
+        "rt_debug_camera_paths_host": (st, [P(Uniforms), P(CameraOpts), vp, C.c_uint32, vp, vp]),
+        "rt_compact_paths": (st, [vp, vp, C.c_uint32, C.c_uint32, P(CompactStream), C.c_uint32, vp, vp]),
+        "rt_compact_paths_on": (st, [vp, vp, C.c_uint32, C.c_uint32, P(CompactStream), C.c_uint32, vp, vp, vp]),
+        "rt_debug_compact_paths_host": (st, [vp, C.c_uint32, C.c_uint32, P(CompactStream), C.c_uint32, vp, vp]),
+        "rt_connect_paths": (st, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32]),
+        "rt_connect_paths_on": (st, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]),
+        "rt_retire_paths": (st, [vp, vp, C.c_uint32, vp, C.c_uint32]),
+        "rt_retire_paths_on": (st, [vp, vp, C.c_uint32, vp, C.c_uint32, vp]),
+        "rt_average_samples": (st, [vp, vp, C.c_uint32, C.c_uint32, vp]),
+        "rt_average_samples_on": (st, [vp, vp, C.c_uint32, C.c_uint32, vp, vp]),
         "rt_version": (C.c_char_p, []),
         "rt_debug_trace_host": (st, [P(SceneDesc), P(C.c_float), P(C.c_float), C.c_uint32, C.c_int32, P(C.c_float),
                                      P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32)]),

@@ -4,11 +4,15 @@
 // `intersector.intersect` called outside raytracingKernel.  rt_resolve_hits enqueues one
 // rq_resolve launch that turns rays and their hit records into surface and material records, by
 // the same generation rule, and rt_shade_hits one rq_shade launch that turns those records and the
-// path states into the paths' next rays (lights and Halton table only).  Queries share nothing writable with frames: their counters, events
-// and statistics are their own (QuerySlot, rt_ctx.h).
+// path states into the paths' next rays (lights and Halton table only).  The path queries
+// (rt_camera_paths, rt_compact_paths, rt_connect_paths, rt_retire_paths, rt_average_samples) close
+// that loop, each one slot and one launch (the compaction: three, on the slot's own scratch).
+// Queries share nothing writable with frames: their counters, events and statistics are their own
+// (QuerySlot, rt_ctx.h).
 #include <algorithm>
 #include <cstring>
 
+#include "rt_paths.h"
 #include "rt_scene_host.h"
 
 using namespace rt;
@@ -214,6 +218,129 @@ rt_status shade(rt_ctx* c, const rt_shade_opts* o, const rt_ray* rays, const rt_
     HIPC(c, hipGetLastError());
     return commit_query(c, *qp, stream, true);   // as a resolve: `done` only, nothing folded
 }
+
+// ---- path queries: each takes a slot as a resolve does (`done` only, nothing folded) ---------------
+unsigned path_blocks(uint32_t n) { return std::min(path_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u); }
+
+rt_status camera_paths(rt_ctx* c, const Uniforms* u, const rt_camera_opts* o, const uint32_t* random, uint32_t n,
+                       rt_ray* rays, rt_path* paths, hipStream_t stream, bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (rt_status st = validate_camera(c, u, o, random, n, rays, paths)) return st;
+    if (!random) {
+        if (!c->width) FAIL(c, RT_ERR_STATE, "rt_camera_paths without offsets before rt_resize");
+        if (u->width != c->width || u->height != c->height)
+            FAIL(c, RT_ERR_STATE, "uniforms size != the size of the context's offsets (rt_resize)");
+        random = (const uint32_t*)c->d_random.p;
+    }
+    if (n == 0) return RT_OK;
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;   // no geometry is read
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    CamParams P;
+    P.U = *u;
+    P.random = random;
+    P.halton = (const HaltonDim*)c->d_halton.p;
+    P.rays = (float4*)rays;
+    P.paths = (float4*)paths;
+    P.n = n;
+    P.first_pixel = o->first_pixel;
+    P.tag_stride = o->tag_stride;
+    P.tag_offset = o->tag_offset;
+    P.sample = o->sample;
+    launch_camera(P, path_blocks(n), stream);
+    HIPC(c, hipGetLastError());
+    return commit_query(c, *qp, stream, true);
+}
+
+rt_status compact_paths(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
+                        uint32_t stream_count, uint32_t* index, uint32_t* count, hipStream_t stream, bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (rt_status st = validate_compact(c, paths, n, mask, streams, stream_count, index, count)) return st;
+    if (n == 0) return RT_OK;
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;   // no geometry is read
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    QuerySlot& q = *qp;
+    // The slot's own storage: its previous query has been harvested, so nothing reads what a growth
+    // frees.  Grown to the largest size any compaction asked for, so the slots stop growing together.
+    const size_t need = compact_scratch_bytes(n);
+    c->q_scratch_max = std::max(c->q_scratch_max, need);
+    if (q.scratch.bytes < need)
+        if (rt_status st = dev_alloc(c, q.scratch, c->q_scratch_max)) return st;
+    CompactParams P;
+    std::memset(&P, 0, sizeof P);
+    P.paths = (const float4*)paths;
+    for (uint32_t k = 0; k < stream_count; ++k) {
+        P.src[k] = (const float4*)streams[k].src;
+        P.dst[k] = (float4*)streams[k].dst;
+        P.words[k] = streams[k].words;
+    }
+    P.index = index;
+    P.count = count;
+    P.tiles = compact_tiles(n);
+    P.bits = (unsigned long long*)q.scratch.p;
+    P.tile_count = (uint32_t*)(P.bits + (size_t)P.tiles * kCompactSegs);
+    P.n = n;
+    P.mask = mask;
+    P.streams = stream_count;
+    launch_compact(P, std::min(path_resident_blocks(), P.tiles), stream);
+    HIPC(c, hipGetLastError());
+    return commit_query(c, q, stream, true);
+}
+
+rt_status connect_paths(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                        const uint32_t* occluded, uint32_t m, hipStream_t stream, bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (m > 0 && n > 0) {
+        if (!paths || !contrib || !occluded) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+        if ((((uintptr_t)paths | (uintptr_t)contrib) & 15u) || (((uintptr_t)index | (uintptr_t)occluded) & 3u))
+            FAIL(c, RT_ERR_INVALID_ARG, "paths and contrib must be 16-byte aligned, index and occluded 4-byte aligned");
+    }
+    if (m == 0 || n == 0) return RT_OK;
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    const ConnectParams P{(float4*)paths, (const float4*)contrib, index, occluded, n, m};
+    launch_connect(P, path_blocks(m), stream);
+    HIPC(c, hipGetLastError());
+    return commit_query(c, *qp, stream, true);
+}
+
+rt_status retire_paths(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags, hipStream_t stream,
+                       bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (n > 0 && tags > 0) {
+        if (!paths || !samples) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+        if (((uintptr_t)paths | (uintptr_t)samples) & 15u) FAIL(c, RT_ERR_INVALID_ARG, "paths and samples must be 16-byte aligned");
+    }
+    if (n == 0 || tags == 0) return RT_OK;
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    const RetireParams P{(const float4*)paths, (float4*)samples, n, tags};
+    launch_retire(P, path_blocks(n), stream);
+    HIPC(c, hipGetLastError());
+    return commit_query(c, *qp, stream, true);
+}
+
+rt_status average_samples(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba, hipStream_t stream,
+                          bool own_stream) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (spp < 1 || spp > 64) FAIL(c, RT_ERR_INVALID_ARG, "spp outside 1 .. 64");
+    if (pixels > 0) {
+        if (!samples || !rgba) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+        if (((uintptr_t)samples | (uintptr_t)rgba) & 15u) FAIL(c, RT_ERR_INVALID_ARG, "samples and rgba must be 16-byte aligned");
+        if (samples == rgba) FAIL(c, RT_ERR_INVALID_ARG, "in place is not supported");
+    }
+    if (pixels == 0) return RT_OK;
+    QuerySlot* qp = nullptr;
+    const Geo* gp = nullptr;
+    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
+    const AverageParams P{(const float4*)samples, (float4*)rgba, pixels, spp};
+    launch_average(P, path_blocks(pixels), stream);
+    HIPC(c, hipGetLastError());
+    return commit_query(c, *qp, stream, true);
+}
 }  // namespace
 
 rt_status drain_queries(rt_ctx* c) {
@@ -261,6 +388,52 @@ rt_status rt_shade_hits_on(rt_ctx* c, const rt_shade_opts* opts, const rt_ray* r
                            rt_ray* next_rays, rt_ray* shadow_rays, float* contrib, void* stream) {
     return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib,
                  (hipStream_t)stream, false);
+}
+
+rt_status rt_camera_paths(rt_ctx* c, const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
+                          uint32_t n, rt_ray* rays, rt_path* paths) {
+    return camera_paths(c, u, opts, random_offsets, n, rays, paths, nullptr, true);
+}
+
+rt_status rt_camera_paths_on(rt_ctx* c, const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
+                             uint32_t n, rt_ray* rays, rt_path* paths, void* stream) {
+    return camera_paths(c, u, opts, random_offsets, n, rays, paths, (hipStream_t)stream, false);
+}
+
+rt_status rt_compact_paths(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
+                           uint32_t stream_count, uint32_t* index, uint32_t* count) {
+    return compact_paths(c, paths, n, mask, streams, stream_count, index, count, nullptr, true);
+}
+
+rt_status rt_compact_paths_on(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
+                              uint32_t stream_count, uint32_t* index, uint32_t* count, void* stream) {
+    return compact_paths(c, paths, n, mask, streams, stream_count, index, count, (hipStream_t)stream, false);
+}
+
+rt_status rt_connect_paths(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                           const uint32_t* occluded, uint32_t m) {
+    return connect_paths(c, paths, n, contrib, index, occluded, m, nullptr, true);
+}
+
+rt_status rt_connect_paths_on(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                              const uint32_t* occluded, uint32_t m, void* stream) {
+    return connect_paths(c, paths, n, contrib, index, occluded, m, (hipStream_t)stream, false);
+}
+
+rt_status rt_retire_paths(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags) {
+    return retire_paths(c, paths, n, samples, tags, nullptr, true);
+}
+
+rt_status rt_retire_paths_on(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags, void* stream) {
+    return retire_paths(c, paths, n, samples, tags, (hipStream_t)stream, false);
+}
+
+rt_status rt_average_samples(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba) {
+    return average_samples(c, samples, pixels, spp, rgba, nullptr, true);
+}
+
+rt_status rt_average_samples_on(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba, void* stream) {
+    return average_samples(c, samples, pixels, spp, rgba, (hipStream_t)stream, false);
 }
 
 rt_status rt_get_query_stats(rt_ctx* c, rt_query_stats* out) {

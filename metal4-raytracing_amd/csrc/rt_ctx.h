@@ -62,13 +62,15 @@ struct Geo {
     const rt::DevBuf& operator[](Buf b) const { return buf[b]; }
 };
 
-// One device ray query in flight (rt_trace_closest / rt_trace_any / rt_resolve_hits): the launch's
+// One device ray query in flight (rt_trace_closest / rt_trace_any / rt_resolve_hits / rt_shade_hits /
+// the path queries): the launch's
 // own device state (chunk counters and statistics, rt_kernels.h RqParams::state), its pinned copy and its events.
 // Queries rotate over kQuerySlots of these, so launches that may overlap (other streams) share no
 // counter; a slot is reused once its previous query has finished (harvest_query).
 constexpr int kQuerySlots = 4;
 struct QuerySlot {
     rt::DevBuf state;
+    rt::DevBuf scratch;         // rt_compact_paths: the call's selection words and tile counts (rt_paths.h); grown on demand
     rt::Pinned<unsigned long long> h_counters;
     rt::Event ev0, ev1, done;   // around the launch (timing); after the counters' copy
     bool pending = false, any = false;
@@ -153,6 +155,7 @@ struct rt_ctx {
     QuerySlot qslot[kQuerySlots];
     int qnext = 0;                   // the slot the next query takes (the oldest)
     rt::DevBuf d_sub_first;          // first scene-wide triangle id per [mesh * max_sub + submesh]
+    size_t q_scratch_max = 0;        // the largest compaction scratch asked for: a slot that grows grows to this
     rt::Event q_uev;                 // the update stream's state a query's stream waits for
     rt_query_stats qstats{};
     bool q_overflow = false;         // a harvested query overflowed its stack: reported by rt_wait / rt_get_query_stats

@@ -174,6 +174,54 @@ struct ShParams {
 unsigned shade_resident_blocks();
 void launch_shade(const ShParams& P, unsigned blocks, hipStream_t stream);
 
+// Path queries (rq_camera, rq_connect, rq_retire, rq_average and the three rq_compact_* launches,
+// rt_query.hip; per-record code and tile geometry: rt_paths.h).  One thread per record but for the
+// compaction, all records as 16-B words.
+struct CamParams {
+    Uniforms U;
+    const uint32_t* random;    // width * height offsets
+    const HaltonDim* halton;   // the table; entry 1 is read
+    float4* rays;              // two words per record
+    float4* paths;             // three
+    uint32_t n, first_pixel, tag_stride, tag_offset;
+    int sample;
+};
+struct ConnectParams {
+    float4* paths;
+    const float4* contrib;
+    const uint32_t* index;     // or null: j itself
+    const uint32_t* occluded;
+    uint32_t n, m;
+};
+struct RetireParams {
+    const float4* paths;
+    float4* samples;
+    uint32_t n, tags;
+};
+struct AverageParams {
+    const float4* samples;
+    float4* rgba;
+    uint32_t pixels, spp;
+};
+struct CompactParams {
+    const float4* paths;
+    const float4* src[4];
+    float4* dst[4];
+    uint32_t words[4];
+    uint32_t* index;                // or null
+    uint32_t* count;
+    unsigned long long* bits;       // kCompactSegs selection words per tile
+    uint32_t* tile_count;           // per tile: selected count, after the scan its offset
+    uint32_t n, mask, streams, tiles;
+};
+unsigned path_resident_blocks();
+void launch_camera(const CamParams& P, unsigned blocks, hipStream_t stream);
+void launch_connect(const ConnectParams& P, unsigned blocks, hipStream_t stream);
+void launch_retire(const RetireParams& P, unsigned blocks, hipStream_t stream);
+void launch_average(const AverageParams& P, unsigned blocks, hipStream_t stream);
+// the three launches of a compaction; tile_blocks: the grid of the count and the copy launch
+void launch_compact(const CompactParams& P, unsigned tile_blocks, hipStream_t stream);
+
 // Utility kernels (rt_util.hip)
 // G-buffer-guided denoise for RT_SCALER_DENOISED (rt_present.hip); returns tmp0 or tmp1, whichever
 // holds the result (passes = 0 returns the demodulated radiance unremodulated: callers pass >= 1)

@@ -3,10 +3,12 @@
 // traversal of rt_trav.h the way wf_trace (rt_wavefront.hip) is.  The replacement of Metal's
 // `intersector.intersect` called from a kernel other than raytracingKernel.  Next to it the two
 // per-record kernels of a user-side integrator: rq_resolve (rt_resolve_hits) and rq_shade
-// (rt_shade_hits).
+// (rt_shade_hits), and the path queries that close its loop: rq_camera, rq_connect, rq_retire,
+// rq_average and the three launches of rt_compact_paths.
 #include <hip/hip_runtime.h>
 
 #include "rt_kernels.h"
+#include "rt_paths.h"
 #include "rt_scatter.h"
 #include "rt_surface.h"
 #include "rt_trav.h"
@@ -182,7 +184,204 @@ __global__ void __launch_bounds__(kBlock) rq_shade(ShParams P) {
     }
 }
 
+// ---- path queries: camera paths, connect, retire, average -------------------------------------------
+// One record per thread, grid-stride over at most the resident blocks, as rq_shade; every record
+// moves as whole 16-B words, the per-record code is rt_paths.h's.  No LDS, no atomics.
+__global__ void __launch_bounds__(kBlock) rq_camera(CamParams P) {
+    const HaltonDim tab1 = P.halton[1];
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)P.n; i += stride) {
+        const uint32_t pix = P.first_pixel + (uint32_t)i;   // < width * height (checked by the host)
+        CameraWords w;
+        camera_record(P.U, tab1, P.random[pix], pix, P.sample, pix * P.tag_stride + P.tag_offset, w);
+        P.rays[2 * i] = w.r0;
+        P.rays[2 * i + 1] = w.r1;
+        float4* const pp = P.paths + 3 * i;
+        pp[0] = w.p0;
+        pp[1] = w.p1;
+        reinterpret_cast<uint4*>(pp)[2] = w.p2;
+    }
+}
+
+// Shadow ray j (of m) belongs to record index[j] (or j); an unoccluded one adds its record's
+// contribution.  Records at or above n are skipped before anything of theirs is addressed.
+__global__ void __launch_bounds__(kBlock) rq_connect(ConnectParams P) {
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < (size_t)P.m; j += stride) {
+        if (P.occluded[j] != 0u) continue;
+        const size_t i = P.index ? (size_t)P.index[j] : j;
+        if (i >= (size_t)P.n) continue;
+        P.paths[3 * i + 1] = connect_word(P.paths[3 * i + 1], P.contrib[i]);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) rq_retire(RetireParams P) {
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)P.n; i += stride) {
+        const float4 p1 = P.paths[3 * i + 1];
+        const uint32_t tag = reinterpret_cast<const uint4*>(P.paths)[3 * i + 2].w;
+        if ((f2u(p1.w) & RT_PATH_ALIVE) == 0u && tag < P.tags) P.samples[tag] = retire_word(p1);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) rq_average(AverageParams P) {
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x; p < (size_t)P.pixels; p += stride)
+        P.rgba[p] = average_pixel(P.samples + p * P.spp, P.spp);
+}
+
+// ---- path queries: stable compaction ------------------------------------------------------------------
+// Three launches, none of which waits for another block (no look-back, no ticket, no grid
+// barrier): the order of the output is the order of the input whatever order the blocks run in.
+//  1. rq_compact_count: per tile of kCompactTile records, the selection word of each 64-record
+//     segment (a wave's __ballot of (flags & mask) != 0; the flag words sit 48 B apart, so this is
+//     the one launch that touches every line of `paths`) and the tile's selected count.
+//  2. rq_compact_scan: one block turns the tile counts into exclusive offsets, kBlock at a time
+//     with a running carry, and writes *count.
+//  3. rq_compact_copy: per tile, the rank of a selected record is its segment's base (an LDS scan
+//     of the kCompactSegs popcounts) plus mbcnt of the segment's word below its lane; the tile's
+//     selected source indices are staged in LDS in rank order, and consecutive threads then copy
+//     consecutive 16-B words of the tile's contiguous destination range [offset, offset + cnt):
+//     coalesced stores, gathering loads.  It reads the 8-byte words of launch 1, not the flags.
+static_assert(kCompactTile % kBlock == 0 && kBlock % 64 == 0 && kCompactSegs <= kBlock, "tile geometry");
+
+__global__ void __launch_bounds__(kBlock) rq_compact_count(CompactParams P) {
+    __shared__ uint32_t seg_cnt[kCompactSegs];
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t* const flags = reinterpret_cast<const uint32_t*>(P.paths) + 7;   // rt_path.flags, 12 words apart
+    for (uint32_t tile = blockIdx.x; tile < P.tiles; tile += gridDim.x) {
+        const size_t first = (size_t)tile * kCompactTile;
+        #pragma unroll
+        for (uint32_t k = 0; k < kCompactTile / kBlock; ++k) {
+            const size_t i = first + k * kBlock + threadIdx.x;
+            const bool sel = i < (size_t)P.n && (flags[12 * i] & P.mask) != 0u;
+            const unsigned long long b = __ballot(sel);
+            if (lane_id() == 0) {
+                const uint32_t seg = k * (kBlock / 64) + wave;
+                P.bits[(size_t)tile * kCompactSegs + seg] = b;   // segments past n: 0
+                seg_cnt[seg] = (uint32_t)__popcll(b);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t s = 0;
+            #pragma unroll
+            for (uint32_t q = 0; q < kCompactSegs; ++q) s += seg_cnt[q];
+            P.tile_count[tile] = s;
+        }
+        __syncthreads();   // seg_cnt is rewritten by the next tile
+    }
+}
+
+// One block whatever n is.  The total is at most n, so 32 bits hold every offset and the count.
+__global__ void __launch_bounds__(kBlock) rq_compact_scan(CompactParams P) {
+    __shared__ uint32_t wave_tot[kBlock / 64];
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < P.tiles; base += kBlock) {
+        const uint32_t t = base + threadIdx.x;
+        const uint32_t v = t < P.tiles ? P.tile_count[t] : 0u;
+        const uint32_t incl = wave_incl_scan(v);
+        if (lane_id() == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        #pragma unroll
+        for (uint32_t w = 0; w < kBlock / 64; ++w) {
+            before += w < wave ? wave_tot[w] : 0u;
+            total += wave_tot[w];
+        }
+        if (t < P.tiles) P.tile_count[t] = carry + before + (incl - v);
+        carry += total;
+        __syncthreads();   // wave_tot is rewritten by the next round
+    }
+    if (threadIdx.x == 0) *P.count = carry;
+}
+
+// Words [0, cnt * W) of the tile's destination range, thread after thread.
+template <uint32_t W>
+__device__ __forceinline__ void compact_copy_words(const float4* src, float4* dst, const uint32_t* sel_idx, size_t first,
+                                                   size_t base, uint32_t cnt) {
+    for (uint32_t q = threadIdx.x; q < cnt * W; q += kBlock) {
+        const uint32_t j = q / W, w = q - j * W;
+        dst[(base + j) * W + w] = src[(first + sel_idx[j]) * W + w];
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) rq_compact_copy(CompactParams P) {
+    __shared__ unsigned long long seg_word[kCompactSegs];
+    __shared__ uint32_t seg_cnt[kCompactSegs];
+    __shared__ uint32_t seg_base[kCompactSegs + 1];
+    __shared__ uint32_t sel_idx[kCompactTile];   // the tile's selected records (index within the tile) by rank
+    const uint32_t wave = threadIdx.x >> 6;
+    for (uint32_t tile = blockIdx.x; tile < P.tiles; tile += gridDim.x) {
+        const size_t first = (size_t)tile * kCompactTile;
+        if (threadIdx.x < kCompactSegs) {
+            const unsigned long long b = P.bits[(size_t)tile * kCompactSegs + threadIdx.x];
+            seg_word[threadIdx.x] = b;
+            seg_cnt[threadIdx.x] = (uint32_t)__popcll(b);
+        }
+        __syncthreads();
+        if (threadIdx.x <= kCompactSegs) {
+            uint32_t s = 0;
+            for (uint32_t q = 0; q < threadIdx.x; ++q) s += seg_cnt[q];
+            seg_base[threadIdx.x] = s;
+        }
+        __syncthreads();
+        #pragma unroll
+        for (uint32_t k = 0; k < kCompactTile / kBlock; ++k) {
+            const uint32_t seg = k * (kBlock / 64) + wave;
+            const unsigned long long b = seg_word[seg];   // the ballot rq_compact_count took of this wave's records
+            if ((b >> lane_id()) & 1ull) sel_idx[seg_base[seg] + mbcnt64(b)] = k * kBlock + threadIdx.x;   // < cnt <= kCompactTile
+        }
+        __syncthreads();
+        const uint32_t cnt = seg_base[kCompactSegs];
+        const size_t base = P.tile_count[tile];   // the tile's offset (rq_compact_scan)
+        #pragma unroll
+        for (uint32_t s = 0; s < kCompactMaxStreams; ++s) {
+            if (s >= P.streams) break;
+            switch (P.words[s]) {
+                case 1: compact_copy_words<1>(P.src[s], P.dst[s], sel_idx, first, base, cnt); break;
+                case 2: compact_copy_words<2>(P.src[s], P.dst[s], sel_idx, first, base, cnt); break;
+                case 3: compact_copy_words<3>(P.src[s], P.dst[s], sel_idx, first, base, cnt); break;
+                default: compact_copy_words<4>(P.src[s], P.dst[s], sel_idx, first, base, cnt); break;
+            }
+        }
+        if (P.index)
+            for (uint32_t j = threadIdx.x; j < cnt; j += kBlock) P.index[base + j] = (uint32_t)(first + sel_idx[j]);
+        __syncthreads();   // the LDS arrays are rewritten by the next tile
+    }
+}
+
 }  // namespace
+
+unsigned path_resident_blocks() {
+    static const unsigned resident = [] {
+        int dev = 0, cus = 256, per = 0;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        // the kernel that holds the most LDS: one figure serves all
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rq_compact_copy, kBlock, 0) != hipSuccess || per < 1) per = 4;
+        return (unsigned)(cus * per);
+    }();
+    return resident;
+}
+
+void launch_camera(const CamParams& P, unsigned blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(rq_camera, dim3(blocks), dim3(kBlock), 0, stream, P);
+}
+void launch_connect(const ConnectParams& P, unsigned blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(rq_connect, dim3(blocks), dim3(kBlock), 0, stream, P);
+}
+void launch_retire(const RetireParams& P, unsigned blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(rq_retire, dim3(blocks), dim3(kBlock), 0, stream, P);
+}
+void launch_average(const AverageParams& P, unsigned blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(rq_average, dim3(blocks), dim3(kBlock), 0, stream, P);
+}
+void launch_compact(const CompactParams& P, unsigned tile_blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(rq_compact_count, dim3(tile_blocks), dim3(kBlock), 0, stream, P);
+    hipLaunchKernelGGL(rq_compact_scan, dim3(1), dim3(kBlock), 0, stream, P);
+    hipLaunchKernelGGL(rq_compact_copy, dim3(tile_blocks), dim3(kBlock), 0, stream, P);
+}
 
 unsigned shade_resident_blocks() {
     static const unsigned resident = [] {

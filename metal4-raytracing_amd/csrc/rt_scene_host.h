@@ -76,6 +76,51 @@ inline rt_status shade_light_count(rt_ctx* c, const rt_shade_opts* o, uint32_t h
     return RT_OK;
 }
 
+// What rt_camera_paths and rt_debug_camera_paths_host accept of their arguments (the offsets'
+// source apart: the context's own or the caller's).
+inline rt_status validate_camera(rt_ctx* c, const Uniforms* u, const rt_camera_opts* o, const void* random_offsets,
+                                 uint32_t n, const void* rays, const void* paths) {
+    if (!u || !o) FAIL(c, RT_ERR_INVALID_ARG, "null uniforms / opts");
+    if (u->width <= 0 || u->height <= 0 || (int64_t)u->width * u->height > (1ll << 30))
+        FAIL(c, RT_ERR_INVALID_ARG, "bad size");
+    if (o->sample < 0) FAIL(c, RT_ERR_INVALID_ARG, "negative sample");
+    if (o->tag_stride == 0) FAIL(c, RT_ERR_INVALID_ARG, "tag_stride is 0");
+    if ((uint64_t)o->first_pixel + n > (uint64_t)u->width * (uint64_t)u->height)
+        FAIL(c, RT_ERR_INVALID_ARG, "first_pixel + n is past the image");
+    if (n > 0 && (!rays || !paths)) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+    if ((((uintptr_t)rays | (uintptr_t)paths) & 15u) || ((uintptr_t)random_offsets & 3u))
+        FAIL(c, RT_ERR_INVALID_ARG, "rays and paths must be 16-byte aligned, random_offsets 4-byte aligned");
+    return RT_OK;
+}
+
+// What rt_compact_paths and rt_debug_compact_paths_host accept.  Overlap cannot be checked in
+// full: equal base pointers are.
+inline rt_status validate_compact(rt_ctx* c, const void* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
+                                  uint32_t stream_count, const void* index, const void* count) {
+    if (mask == 0) FAIL(c, RT_ERR_INVALID_ARG, "mask is 0");
+    if (stream_count > 4) FAIL(c, RT_ERR_INVALID_ARG, "more than 4 streams");
+    if (stream_count > 0 && !streams) FAIL(c, RT_ERR_INVALID_ARG, "null streams");
+    for (uint32_t k = 0; k < stream_count; ++k)
+        if (streams[k].words < 1 || streams[k].words > 4) FAIL(c, RT_ERR_INVALID_ARG, "stream words outside 1 .. 4");
+    if (n == 0) return RT_OK;
+    if (!paths || !count) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+    if (((uintptr_t)paths & 15u) || (((uintptr_t)index | (uintptr_t)count) & 3u))
+        FAIL(c, RT_ERR_INVALID_ARG, "paths must be 16-byte aligned, index and count 4-byte aligned");
+    if (count == paths || count == index || (index && index == paths))
+        FAIL(c, RT_ERR_INVALID_ARG, "index, count and paths overlap");
+    for (uint32_t k = 0; k < stream_count; ++k) {
+        const rt_compact_stream& s = streams[k];
+        if (!s.src || !s.dst) FAIL(c, RT_ERR_INVALID_ARG, "null stream pointer");
+        if (((uintptr_t)s.src | (uintptr_t)s.dst) & 15u) FAIL(c, RT_ERR_INVALID_ARG, "stream pointers must be 16-byte aligned");
+        if (s.dst == paths || s.dst == index || s.dst == count || s.src == count || (index && s.src == index))
+            FAIL(c, RT_ERR_INVALID_ARG, "a stream overlaps paths, index or count (in place is not supported)");
+        for (uint32_t j = 0; j < stream_count; ++j)
+            if (s.dst == streams[j].src || (j != k && s.dst == streams[j].dst))
+                FAIL(c, RT_ERR_INVALID_ARG, "a dst equals a src or another dst (in place is not supported)");
+    }
+    return RT_OK;
+}
+
 // A scene description flattened mesh by mesh: positions and normals with every mesh's vertices
 // after the previous one's, triangles as (three vertex ids, mesh << 8 | submesh), 12 floats of
 // transform per mesh.  nrm may be null.

@@ -29,7 +29,23 @@ timed runs each child does one counting run for the node visits and triangle tes
     launch with the caller's numbers (uniform random, 32 B more per record: 336 B) in place of the
     Halton draws, which tells the cost of the Halton digit loops from that of the traffic.
 
-    python tools/query_bench.py [--resolve | --shade] [--scene c3g] [--width 1920] [--height 1080] [--run-timeout 60]
+--loop runs leg (e) in one child and prints one JSON line:
+(e) loop: the whole frame (frame 0 at --spp samples and --bounces bounces, the bench's 4 and 8)
+    four ways on one build, one renderer, one session: Renderer.path_trace (library calls only:
+    camera_paths, then trace / resolve / shade / compact / trace_any / connect / retire / compact
+    per round, then average); the torch-glue loop of tests/shade_ref.py integrate / render on the
+    device (per sample: boolean-index selection of the shadow rays, torch.where for the add, a
+    torch sum for the pixel) in its carry form (dead records kept) and in its boolean-index
+    compaction form; and Renderer.draw (rt_render_frame) for scale.  Each is timed by the wall
+    clock around one frame that ends with a device synchronisation, median of five after two
+    warm-up runs; rate = (closest-hit + shadow rays of the frame) / time.  The three query images
+    are compared bit for bit.  Then rt_compact_paths alone on round 0's records of path_trace's
+    batch, in the loop's two shapes (SHADOW: shadow rays + index; ALIVE: next rays + paths), timed by
+    HIP events on a stream of its own (median of five after two), as a share of its HBM floor at
+    6.3 TB/s: every line of `paths` read once for the flag words (48 n), the selection words
+    written and read (n / 8 each), m x 16 x words read and the same written, 4 m of index.
+
+    python tools/query_bench.py [--resolve | --shade | --loop] [--scene c3g] [--width 1920] [--height 1080] [--run-timeout 60]
 """
 import argparse
 import importlib
@@ -207,10 +223,135 @@ def child_shade(args):
     return 0
 
 
+def glue_integrate(rt, R, rays, paths, max_bounces, compact, stream=0):
+    """tests/shade_ref.py integrate with its DeviceBackend: the bounce loop over one sample's paths
+    with torch between the queries.  Returns (radiance (n, 3), closest rays, shadow rays)."""
+    import numpy as np
+    import torch
+    n, dev = len(paths), rays.device
+    index = torch.arange(n, device=dev)
+    radiance = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+    miss = torch.from_numpy(np.array([0x7F800000, 0, 0] + [0xFFFFFFFF] * 4 + [0], np.uint32).view(np.float32)).to(dev)
+    closest = shadow = 0
+    guard = max_bounces * (max_bounces + 1) + 1
+    for it in range(guard + 1):
+        alive = paths.alive
+        na = int(alive.sum().item())
+        if na == 0:
+            break
+        if it >= guard:
+            raise RuntimeError("a path outlived the renderer's longest")
+        if compact:
+            radiance[index[~alive]] = paths.radiance[~alive]
+            pb = paths.buffer[alive]
+            rays, index, paths = rays[alive], index[alive], rt.Paths(pb, pb.view(torch.int32))
+            hits = R.trace(rays, stream=stream).buffer
+        else:
+            hits = miss.expand(n, 8).contiguous()
+            hits[alive] = R.trace(rays[alive], stream=stream).buffer
+        closest += na
+        S = R.resolve(rays, hits, stream=stream)
+        out = R.shade(rays, S, paths, stream=stream)
+        sh = paths.shadow
+        ns = int(sh.sum().item())
+        if ns:
+            occluded = R.trace(out.shadow_rays[sh], any_hit=True, stream=stream)
+            lit = sh.clone()
+            lit[sh] = occluded == 0
+            paths.radiance[:] = torch.where(lit[:, None], paths.radiance + out.contrib[:, 0:3], paths.radiance)
+        shadow += ns
+        rays = out.next_rays
+    radiance[index] = paths.radiance
+    return radiance, closest, shadow
+
+
+def glue_render(rt, R, spp, max_bounces, compact):
+    """tests/shade_ref.py render on the device: per sample the camera records and glue_integrate,
+    then pixel = (sum in sample order) / spp.  Returns ((H * W, 3) image, closest, shadow)."""
+    total, closest, shadow = None, 0, 0
+    u = R.uniforms()
+    u.frameIndex = 0
+    for s in range(spp):
+        rays, paths = R.camera_paths(s, uniforms=u, stream=0)
+        rad, nc, ns = glue_integrate(rt, R, rays, paths, max_bounces, compact)
+        total = rad if total is None else total + rad
+        closest, shadow = closest + nc, shadow + ns
+    return total / float(spp), closest, shadow
+
+
+COMPACT_SHAPES = {"shadow": (2, (2,), True), "alive": (1, (2, 3), False)}   # mask, stream words, index
+
+
+def child_loop(args):
+    rt = _rt()
+    import torch
+    W, H, spp, mb = args.width, args.height, args.spp, args.bounces
+    R = rt.Renderer(rt.Scene.preset(args.scene), W, H, frames_in_flight=1)
+    R.samplesPerPixel, R.maxBounces = spp, mb
+    dev = torch.device("cuda", 0)
+    _emit(ready=True)
+    images = {}
+
+    def frame():
+        R.samplesPerPixel = spp   # resets frameIndex: every run is frame 0
+        R.draw()
+        R.wait()
+        st = R.stats()
+        return int(st.closest_rays + st.shadow_rays)
+
+    def loop():
+        images["loop"] = R.path_trace()
+        t = R.last_path_trace
+        return t["closest_rays"] + t["shadow_rays"]
+
+    def glue(compact):
+        img, nc, ns = glue_render(rt, R, spp, mb, compact)
+        images["glue_compact" if compact else "glue_carry"] = img
+        return nc + ns
+
+    for kind, fn in (("frame", frame), ("loop", loop), ("glue_carry", lambda: glue(False)), ("glue_compact", lambda: glue(True))):
+        for k in range(WARMUP + RUNS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rays = fn()
+            torch.cuda.synchronize()
+            _emit(run=k, kind=kind, rays=int(rays), ms=(time.perf_counter() - t0) * 1e3)
+    rgb = images["loop"].reshape(-1, 4)[:, 0:3].contiguous().view(torch.int32)
+    _emit(images=True, equal=bool(torch.equal(rgb, images["glue_carry"].contiguous().view(torch.int32))
+                                  and torch.equal(rgb, images["glue_compact"].contiguous().view(torch.int32))),
+          rounds=R.last_path_trace["rounds"])
+    # round 0 of the batch: every sample's camera paths, traced, resolved and shaded once
+    del images
+    R._pt_buffers = None
+    torch.cuda.empty_cache()
+    n = W * H * spp
+    rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    pb = torch.empty((n, 12), dtype=torch.float32, device=dev)
+    for s in range(spp):
+        R.camera_paths(s, tag_stride=spp, tag_offset=s, out=(rays[s * W * H:(s + 1) * W * H], pb[s * W * H:(s + 1) * W * H]), stream=0)
+    out = R.shade(rays, R.resolve(rays, R.trace(rays, stream=0), stream=0), pb, stream=0)
+    src = {2: out.shadow_rays, 3: pb}
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.synchronize()
+    for kind, (mask, words, index) in COMPACT_SHAPES.items():
+        streams = [out.next_rays if (w == 2 and kind == "alive") else src[w] for w in words]
+        c = R.compact(pb, mask, streams, index=index, stream=stream.cuda_stream)
+        m = c.n()
+        for k in range(WARMUP + RUNS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            R.compact(pb, mask, streams, index=index, out=c, stream=stream.cuda_stream)
+            e1.record(stream)
+            e1.synchronize()
+            _emit(run=k, kind="compact_" + kind, records=n, selected=m, ms=float(e0.elapsed_time(e1)))
+    R.close()
+    return 0
+
+
 def run_child(kind, args):
     """The child's reports; every line has to arrive within its time limit."""
     cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--scene", args.scene, "--width", str(args.width),
-           "--height", str(args.height)]
+           "--height", str(args.height), "--spp", str(args.spp), "--bounces", str(args.bounces)]
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE)
     fd = p.stdout.fileno()
     sel = selectors.DefaultSelector()
@@ -247,6 +388,48 @@ def run_child(kind, args):
     return lines, None
 
 
+def main_loop(args):
+    n = args.width * args.height * args.spp
+    res = {"scene": args.scene, "width": args.width, "height": args.height, "spp": args.spp, "bounces": args.bounces, "paths": n,
+           "method": f"each leg: {WARMUP} warm-up runs, then the median of {RUNS}; frames by the wall clock around one frame "
+                     "ending in a device synchronisation, Grays/s = (closest-hit + shadow rays) / time; compactions by "
+                     f"HIP events around the call on its stream, floor at {HBM_BYTES_PER_S / 1e12} TB/s"}
+    lines, err = run_child("loop", args)
+    legs = ["frame", "loop", "glue_carry", "glue_compact"] + ["compact_" + k for k in COMPACT_SHAPES]
+    for kind in legs:
+        runs = [r for r in lines if r.get("kind") == kind and r["run"] >= WARMUP]
+        if not err and len(runs) != RUNS:
+            err = f"loop ({kind}): {len(runs)} timed runs reported, not {RUNS}"
+        if err:
+            res["error"] = err
+            print(json.dumps(res))
+            return 1
+        res[f"{kind}_ms"] = round(statistics.median(r["ms"] for r in runs), 4)
+        res[f"{kind}_runs_ms"] = [round(r["ms"], 4) for r in runs]
+        if kind.startswith("compact_"):
+            mask, words, index = COMPACT_SHAPES[kind[8:]]
+            m = runs[-1]["selected"]
+            moved = 16 * sum(words)
+            nbytes = 48 * n + 2 * (n // 8) + 2 * m * moved + (4 * m if index else 0)
+            res[f"{kind}_selected_share"] = round(m / n, 4)
+            res[f"{kind}_floor_bytes"] = nbytes
+            res[f"{kind}_floor_ms"] = round(nbytes / HBM_BYTES_PER_S * 1e3, 4)
+            res[f"{kind}_floor_fraction"] = round(nbytes / HBM_BYTES_PER_S * 1e3 / res[f"{kind}_ms"], 4)
+        else:
+            rates = [r["rays"] / r["ms"] * 1e-6 for r in runs]
+            res[f"{kind}_rays"] = runs[-1]["rays"]
+            res[f"{kind}_grays"] = round(statistics.median(rates), 4)
+            res[f"{kind}_runs_grays"] = [round(x, 4) for x in rates]
+    for r in lines:
+        if r.get("images"):
+            res["query_images_bit_equal"] = r["equal"]
+            res["loop_rounds"] = r["rounds"]
+    best = max(res["glue_carry_grays"], res["glue_compact_grays"])
+    res["loop_over_best_glue"] = round(res["loop_grays"] / best, 4)
+    print(json.dumps(res))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="c3g")
@@ -256,11 +439,17 @@ def main():
     ap.add_argument("--setup-timeout", type=float, default=240.0, help="seconds the scene load and BVH build may take")
     ap.add_argument("--resolve", action="store_true", help="leg (c) only: the surface query on leg (b)'s hits")
     ap.add_argument("--shade", action="store_true", help="legs (c, with materials) and (d): the shading query on (c)'s records")
-    ap.add_argument("--child", choices=["frame", "query", "resolve", "shade"])
+    ap.add_argument("--loop", action="store_true", help="leg (e): the whole frame from queries against the torch-glue loop")
+    ap.add_argument("--spp", type=int, default=4, help="--loop: samples per pixel (the bench's 4)")
+    ap.add_argument("--bounces", type=int, default=8, help="--loop: bounces (the bench's 8)")
+    ap.add_argument("--child", choices=["frame", "query", "resolve", "shade", "loop"])
     args = ap.parse_args()
     if args.child:
-        return {"frame": child_frame, "query": child_query, "resolve": child_resolve, "shade": child_shade}[args.child](args)
+        return {"frame": child_frame, "query": child_query, "resolve": child_resolve, "shade": child_shade,
+                "loop": child_loop}[args.child](args)
     res = {"scene": args.scene, "width": args.width, "height": args.height, "rays": args.width * args.height * 4}
+    if args.loop:
+        return main_loop(args)
     if args.resolve or args.shade:
         lines, err = run_child("shade" if args.shade else "resolve", args)
         legs = {"surface_material": RESOLVE_BYTES["surface_material"], "shade": SHADE_BYTES,
