@@ -324,6 +324,10 @@ EXPORTED_SYMBOLS = [
 ]
 
 
+# Entry points with an `_on` twin: the same arguments plus a trailing HIP stream handle (void*).
+ON_TWINS = ("rt_pack_tiles", "rt_unpack_tiles", "rt_trace_closest", "rt_trace_any", "rt_resolve_hits", "rt_shade_hits",
+            "rt_camera_paths", "rt_compact_paths", "rt_connect_paths", "rt_retire_paths", "rt_average_samples")
+
 # entry points a library built from an older revision may lack without losing any compute path
 OPTIONAL = {"rt_set_device_spans"}
 
@@ -353,10 +357,8 @@ def declare(lib):
         "rt_tile_count": (C.c_int32, [C.c_int32, C.c_int32, P(TileSet)]),
         "rt_pack_tiles": (st, [vp, P(TileSet), vp]),
         "rt_unpack_tiles": (st, [vp, P(TileSet), vp]),
-        "rt_pack_tiles_on": (st, [vp, P(TileSet), vp, vp]),
         "rt_present": (st, [vp, P(PresentOpts), vp]),
         "rt_write_png": (st, [C.c_char_p, vp, C.c_uint32, C.c_uint32]),
-        "rt_unpack_tiles_on": (st, [vp, P(TileSet), vp, vp]),
         "rt_pack_tiles_host": (st, [C.c_int32, C.c_int32, P(TileSet), P(C.c_float), P(C.c_float)]),
         "rt_unpack_tiles_host": (st, [C.c_int32, C.c_int32, P(TileSet), P(C.c_float), P(C.c_float)]),
         "rt_set_counting": (st, [vp, C.c_int32]),
@@ -367,27 +369,18 @@ def declare(lib):
         "rt_get_tuning": (st, [vp, P(Tuning)]),
         "rt_trace_closest": (st, [vp, vp, C.c_uint32, vp]),
         "rt_trace_any": (st, [vp, vp, C.c_uint32, vp]),
-        "rt_trace_closest_on": (st, [vp, vp, C.c_uint32, vp, vp]),
-        "rt_trace_any_on": (st, [vp, vp, C.c_uint32, vp, vp]),
         "rt_get_query_stats": (st, [vp, P(QueryStats)]),
         "rt_resolve_hits": (st, [vp, vp, vp, C.c_uint32, vp, vp]),
-        "rt_resolve_hits_on": (st, [vp, vp, vp, C.c_uint32, vp, vp, vp]),
         "rt_debug_resolve_host": (st, [P(SceneDesc), vp, vp, C.c_uint32, vp, vp]),
         "rt_shade_hits": (st, [vp, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
-        "rt_shade_hits_on": (st, [vp, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
         "rt_debug_shade_host": (st, [P(Light), C.c_uint32, P(ShadeOpts), vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
         "rt_camera_paths": (st, [vp, P(Uniforms), P(CameraOpts), vp, C.c_uint32, vp, vp]),
-        "rt_camera_paths_on": (st, [vp, P(Uniforms), P(CameraOpts), vp, C.c_uint32, vp, vp, vp]),
         "rt_debug_camera_paths_host": (st, [P(Uniforms), P(CameraOpts), vp, C.c_uint32, vp, vp]),
         "rt_compact_paths": (st, [vp, vp, C.c_uint32, C.c_uint32, P(CompactStream), C.c_uint32, vp, vp]),
-        "rt_compact_paths_on": (st, [vp, vp, C.c_uint32, C.c_uint32, P(CompactStream), C.c_uint32, vp, vp, vp]),
         "rt_debug_compact_paths_host": (st, [vp, C.c_uint32, C.c_uint32, P(CompactStream), C.c_uint32, vp, vp]),
         "rt_connect_paths": (st, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32]),
-        "rt_connect_paths_on": (st, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]),
         "rt_retire_paths": (st, [vp, vp, C.c_uint32, vp, C.c_uint32]),
-        "rt_retire_paths_on": (st, [vp, vp, C.c_uint32, vp, C.c_uint32, vp]),
         "rt_average_samples": (st, [vp, vp, C.c_uint32, C.c_uint32, vp]),
-        "rt_average_samples_on": (st, [vp, vp, C.c_uint32, C.c_uint32, vp, vp]),
         "rt_version": (C.c_char_p, []),
         "rt_debug_trace_host": (st, [P(SceneDesc), P(C.c_float), P(C.c_float), C.c_uint32, C.c_int32, P(C.c_float),
                                      P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32)]),
@@ -415,6 +408,8 @@ def declare(lib):
         "rt_uniforms_default": (None, [C.c_int32, C.c_int32, C.c_int32, P(Uniforms)]),
         "rt_random_offsets": (None, [C.c_uint64, C.c_int32, C.c_int32, P(C.c_uint32)]),
     }
+    for name in ON_TWINS:
+        sig[name + "_on"] = (sig[name][0], sig[name][1] + [vp])
     for name, (res, args) in sig.items():
         if name in OPTIONAL and not hasattr(lib, name):
             continue   # measurement hook absent from an older library (A/B runs); compute entry points are required

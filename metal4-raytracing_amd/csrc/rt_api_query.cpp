@@ -7,8 +7,9 @@
 // path states into the paths' next rays (lights and Halton table only).  The path queries
 // (rt_camera_paths, rt_compact_paths, rt_connect_paths, rt_retire_paths, rt_average_samples) close
 // that loop, each one slot and one launch (the compaction: three, on the slot's own scratch).
-// Queries share nothing writable with frames: their counters, events and statistics are their own
-// (QuerySlot, rt_ctx.h).
+// Every entry point is its argument checks, then enqueue_query around the parameter fill and the
+// launch.  Queries share nothing writable with frames: their counters, events and statistics are
+// their own (QuerySlot, rt_ctx.h).
 #include <algorithm>
 #include <cstring>
 
@@ -25,7 +26,7 @@ rt_status harvest_query(rt_ctx* c, int k) {
     if (!q.pending) return RT_OK;
     q.pending = false;
     HIPC(c, hipEventSynchronize(q.done));
-    if (q.resolve) return RT_OK;   // a surface query: waited for, not part of rt_query_stats
+    if (!q.counted) return RT_OK;   // waited for, not part of rt_query_stats
     float ms = 0.0f;
     HIPC(c, hipEventElapsedTime(&ms, q.ev0, q.ev1));
     const unsigned long long* hc = q.h_counters.get();
@@ -64,16 +65,23 @@ rt_status ensure_query_slot(rt_ctx* c, QuerySlot& q) {
     return RT_OK;
 }
 
+// Where a query runs: the context's stream (the plain entry points), or the stream the caller
+// gave as it is, the null stream included (the _on entry points).
+struct QueryStream {
+    hipStream_t s;
+    bool own;
+    static QueryStream of_ctx() { return {nullptr, true}; }
+    static QueryStream on(void* stream) { return {(hipStream_t)stream, false}; }
+};
+
 // What every query does before its launch: takes the oldest slot (its previous query, kQuerySlots
-// back, has finished) and makes `stream` wait for the geometry the next frame would read: the
+// back, has finished) and makes the stream wait for the geometry the next frame would read: the
 // generation updates since the newest frame went into (after the update stream's work so far),
-// else the one frames read (after the event of the flip that made it current).  Returns that
-// generation; the caller launches on `stream`, records q->done and calls commit_query.
-// own_stream: the ctx stream (the plain entry points); otherwise `stream` as the caller gave it,
-// the null stream included.
-rt_status begin_query(rt_ctx* c, hipStream_t& stream, bool own_stream, QuerySlot*& q, const Geo*& geo) {
+// else the one frames read (after the event of the flip that made it current).  Gives the stream,
+// the slot and that generation.
+rt_status begin_query(rt_ctx* c, QueryStream where, hipStream_t& stream, QuerySlot*& q, const Geo*& geo) {
     HIPC(c, hipSetDevice(c->device));
-    if (own_stream) stream = c->stream;
+    stream = where.own ? c->stream : where.s;
     q = &c->qslot[c->qnext];
     rt_status st = harvest_query(c, c->qnext);
     if (!st) st = ensure_query_slot(c, *q);
@@ -90,15 +98,32 @@ rt_status begin_query(rt_ctx* c, hipStream_t& stream, bool own_stream, QuerySlot
 }
 
 // After the launch: `done` marks its end for updates, rt_wait and rt_destroy (drain_queries).
-rt_status commit_query(rt_ctx* c, QuerySlot& q, hipStream_t stream, bool resolve) {
+rt_status commit_query(rt_ctx* c, QuerySlot& q, hipStream_t stream, bool counted) {
     HIPC(c, hipEventRecord(q.done, stream));
     q.pending = true;
-    q.resolve = resolve;
+    q.counted = counted;
     c->qnext = (c->qnext + 1) % kQuerySlots;
     return RT_OK;
 }
 
-rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, hipStream_t stream, bool own_stream) {
+// One query around its launch: begin_query, then body(slot, geometry, stream), which fills the
+// parameters and launches on that stream, then the launch's error and commit_query.  counted: the
+// body took the slot's events and counters for rt_query_stats (the traces).
+template <class Body>
+rt_status enqueue_query(rt_ctx* c, QueryStream where, bool counted, Body body) {
+    hipStream_t stream = nullptr;
+    QuerySlot* q = nullptr;
+    const Geo* geo = nullptr;
+    if (rt_status st = begin_query(c, where, stream, q, geo)) return st;
+    if (rt_status st = body(*q, *geo, stream)) return st;
+    HIPC(c, hipGetLastError());
+    return commit_query(c, *q, stream, counted);
+}
+
+// a small batch does not launch the whole chip
+unsigned query_grid(unsigned resident, uint32_t n) { return std::min(resident, (n - 1u) / (unsigned)kBlock + 1u); }
+
+rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (n > 0) {
         if (!rays || !out) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
@@ -107,43 +132,38 @@ rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, 
     }
     if (!c->bvh_ready) FAIL(c, RT_ERR_STATE, "ray query before rt_bvh_build");
     if (n == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    QuerySlot& q = *qp;
-    const Geo& geo = *gp;
-    DevScene S;
-    std::memset(&S, 0, sizeof S);   // the traversal reads the tree, the triangles and tri_info only
-    S.tris = (const float*)geo[Geo::tris].p;
-    S.nodes8 = (const Bvh8Node*)geo[Geo::nodes].p;
-    S.tri_info = (const uint4*)c->d_tri_info.p;
-    S.max_submeshes = c->max_sub;
-    S.num_tris = (int)c->num_tris;
-    S.num_nodes8 = (int)geo.num_nodes8;
-    RqParams Q;
-    Q.rays = (const float4*)rays;
-    Q.hits = any ? nullptr : (float4*)out;
-    Q.occluded = any ? (uint32_t*)out : nullptr;
-    Q.sub_first = (const uint32_t*)c->d_sub_first.p;
-    Q.state = (unsigned long long*)q.state.p;
-    Q.n = n;
-    Q.refill_min = c->tuning.refill_min;
-    // a small batch does not launch the whole chip
-    const unsigned blocks = std::min(query_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u);
-    HIPC(c, hipMemsetAsync(q.state.p, 0, kRqStateBytes, stream));
-    HIPC(c, hipEventRecord(q.ev0, stream));
-    launch_query(S, Q, any, c->counting, blocks, stream);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(q.ev1, stream));
-    HIPC(c, hipMemcpyAsync(q.h_counters, q.state.p, sizeof(unsigned long long) * kCounterWords, hipMemcpyDeviceToHost,
-                           stream));
-    q.any = any;
-    q.blocks = blocks;
-    return commit_query(c, q, stream, false);
+    return enqueue_query(c, where, true, [&](QuerySlot& q, const Geo& geo, hipStream_t stream) -> rt_status {
+        DevScene S;
+        std::memset(&S, 0, sizeof S);   // the traversal reads the tree, the triangles and tri_info only
+        S.tris = (const float*)geo[Geo::tris].p;
+        S.nodes8 = (const Bvh8Node*)geo[Geo::nodes].p;
+        S.tri_info = (const uint4*)c->d_tri_info.p;
+        S.max_submeshes = c->max_sub;
+        S.num_tris = (int)c->num_tris;
+        S.num_nodes8 = (int)geo.num_nodes8;
+        RqParams Q;
+        Q.rays = (const float4*)rays;
+        Q.hits = any ? nullptr : (float4*)out;
+        Q.occluded = any ? (uint32_t*)out : nullptr;
+        Q.sub_first = (const uint32_t*)c->d_sub_first.p;
+        Q.state = (unsigned long long*)q.state.p;
+        Q.n = n;
+        Q.refill_min = c->tuning.refill_min;
+        q.any = any;
+        q.blocks = query_grid(query_resident_blocks(), n);
+        HIPC(c, hipMemsetAsync(q.state.p, 0, kRqStateBytes, stream));
+        HIPC(c, hipEventRecord(q.ev0, stream));
+        launch_query(S, Q, any, c->counting, q.blocks, stream);
+        HIPC(c, hipGetLastError());   // here too: before the calls below can replace it
+        HIPC(c, hipEventRecord(q.ev1, stream));
+        HIPC(c, hipMemcpyAsync(q.h_counters, q.state.p, sizeof(unsigned long long) * kCounterWords, hipMemcpyDeviceToHost,
+                               stream));
+        return RT_OK;
+    });
 }
 
 rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
-                  rt_surface_material* materials, hipStream_t stream, bool own_stream) {
+                  rt_surface_material* materials, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (n > 0) {
         if (!rays || !hits || !surfaces) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
@@ -152,42 +172,39 @@ rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_
     }
     if (!c->bvh_ready) FAIL(c, RT_ERR_STATE, "surface query before rt_bvh_build");
     if (n == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    const Geo& geo = *gp;
-    DevScene S;
-    std::memset(&S, 0, sizeof S);   // surface_eval reads the shading streams only, not the tree
-    S.pos = (const float4*)geo[Geo::pos].p;
-    S.tri_nrm = (const float4*)geo[Geo::tri_nrm].p;
-    S.inst = (const float*)geo[Geo::inst].p;
-    S.materials = (const Material*)c->d_mat.p;
-    S.max_submeshes = c->max_sub;
-    S.num_materials = (int)c->h_mat.size();
-    S.num_tris = (int)c->num_tris;
-    S.textured = c->textured ? 1 : 0;
-    if (c->textured) {
-        S.tex_texels = (const uchar4*)c->d_tex_texels.p;
-        S.tex_info = (const uint4*)c->d_tex_info.p;
-        S.mat_tex = (const int4*)c->d_mat_tex.p;
-        S.uv = (const float2*)c->d_uv.p;
-        S.tex_lut = (const float*)c->d_tex_lut.p;
-    }
-    RsParams P;
-    P.rays = (const float4*)rays;
-    P.hits = (const float4*)hits;
-    P.surfaces = (float4*)surfaces;
-    P.materials = (float4*)materials;
-    P.n = n;
-    const unsigned blocks = std::min(resolve_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u);
-    launch_resolve(S, P, blocks, stream);
-    HIPC(c, hipGetLastError());
-    return commit_query(c, *qp, stream, true);
+    return enqueue_query(c, where, false, [&](QuerySlot&, const Geo& geo, hipStream_t stream) -> rt_status {
+        DevScene S;
+        std::memset(&S, 0, sizeof S);   // surface_eval reads the shading streams only, not the tree
+        S.pos = (const float4*)geo[Geo::pos].p;
+        S.tri_nrm = (const float4*)geo[Geo::tri_nrm].p;
+        S.inst = (const float*)geo[Geo::inst].p;
+        S.materials = (const Material*)c->d_mat.p;
+        S.max_submeshes = c->max_sub;
+        S.num_materials = (int)c->h_mat.size();
+        S.num_tris = (int)c->num_tris;
+        S.textured = c->textured ? 1 : 0;
+        if (c->textured) {
+            S.tex_texels = (const uchar4*)c->d_tex_texels.p;
+            S.tex_info = (const uint4*)c->d_tex_info.p;
+            S.mat_tex = (const int4*)c->d_mat_tex.p;
+            S.uv = (const float2*)c->d_uv.p;
+            S.tex_lut = (const float*)c->d_tex_lut.p;
+        }
+        RsParams P;
+        P.rays = (const float4*)rays;
+        P.hits = (const float4*)hits;
+        P.surfaces = (float4*)surfaces;
+        P.materials = (float4*)materials;
+        P.n = n;
+        launch_resolve(S, P, query_grid(resolve_resident_blocks(), n), stream);
+        return RT_OK;
+    });
 }
 
+// From here on no query reads the geometry: shading reads the lights and the Halton table only.
 rt_status shade(rt_ctx* c, const rt_shade_opts* o, const rt_ray* rays, const rt_surface* surfaces,
                 const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths, rt_ray* next_rays,
-                rt_ray* shadow_rays, float* contrib, hipStream_t stream, bool own_stream) {
+                rt_ray* shadow_rays, float* contrib, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (rt_status st = validate_shade(c, o, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib))
         return st;
@@ -195,35 +212,29 @@ rt_status shade(rt_ctx* c, const rt_shade_opts* o, const rt_ray* rays, const rt_
     int lights = 0;
     if (rt_status st = shade_light_count(c, o, (uint32_t)c->h_lights.size(), lights)) return st;
     if (n == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;   // the shading reads no geometry: lights and the Halton table only
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    ShParams P;
-    P.rays = (const float4*)rays;
-    P.surfaces = (const float4*)surfaces;
-    P.materials = (const float4*)materials;
-    P.randoms = (const float4*)randoms;
-    P.paths = (float4*)paths;
-    P.next_rays = (float4*)next_rays;
-    P.shadow_rays = (float4*)shadow_rays;
-    P.contrib = (float4*)contrib;
-    P.lights = (const Light*)c->d_lights.p;
-    P.halton = (const HaltonDim*)c->d_halton.p;
-    P.n = n;
-    P.shading_mode = o->shading_mode;
-    P.max_bounces = o->max_bounces;
-    P.light_count = lights;
-    const unsigned blocks = std::min(shade_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u);
-    launch_shade(P, blocks, stream);
-    HIPC(c, hipGetLastError());
-    return commit_query(c, *qp, stream, true);   // as a resolve: `done` only, nothing folded
+    return enqueue_query(c, where, false, [&](QuerySlot&, const Geo&, hipStream_t stream) -> rt_status {
+        ShParams P;
+        P.rays = (const float4*)rays;
+        P.surfaces = (const float4*)surfaces;
+        P.materials = (const float4*)materials;
+        P.randoms = (const float4*)randoms;
+        P.paths = (float4*)paths;
+        P.next_rays = (float4*)next_rays;
+        P.shadow_rays = (float4*)shadow_rays;
+        P.contrib = (float4*)contrib;
+        P.lights = (const Light*)c->d_lights.p;
+        P.halton = (const HaltonDim*)c->d_halton.p;
+        P.n = n;
+        P.shading_mode = o->shading_mode;
+        P.max_bounces = o->max_bounces;
+        P.light_count = lights;
+        launch_shade(P, query_grid(shade_resident_blocks(), n), stream);
+        return RT_OK;
+    });
 }
 
-// ---- path queries: each takes a slot as a resolve does (`done` only, nothing folded) ---------------
-unsigned path_blocks(uint32_t n) { return std::min(path_resident_blocks(), (n - 1u) / (unsigned)kBlock + 1u); }
-
 rt_status camera_paths(rt_ctx* c, const Uniforms* u, const rt_camera_opts* o, const uint32_t* random, uint32_t n,
-                       rt_ray* rays, rt_path* paths, hipStream_t stream, bool own_stream) {
+                       rt_ray* rays, rt_path* paths, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (rt_status st = validate_camera(c, u, o, random, n, rays, paths)) return st;
     if (!random) {
@@ -233,63 +244,58 @@ rt_status camera_paths(rt_ctx* c, const Uniforms* u, const rt_camera_opts* o, co
         random = (const uint32_t*)c->d_random.p;
     }
     if (n == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;   // no geometry is read
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    CamParams P;
-    P.U = *u;
-    P.random = random;
-    P.halton = (const HaltonDim*)c->d_halton.p;
-    P.rays = (float4*)rays;
-    P.paths = (float4*)paths;
-    P.n = n;
-    P.first_pixel = o->first_pixel;
-    P.tag_stride = o->tag_stride;
-    P.tag_offset = o->tag_offset;
-    P.sample = o->sample;
-    launch_camera(P, path_blocks(n), stream);
-    HIPC(c, hipGetLastError());
-    return commit_query(c, *qp, stream, true);
+    return enqueue_query(c, where, false, [&](QuerySlot&, const Geo&, hipStream_t stream) -> rt_status {
+        CamParams P;
+        P.U = *u;
+        P.random = random;
+        P.halton = (const HaltonDim*)c->d_halton.p;
+        P.rays = (float4*)rays;
+        P.paths = (float4*)paths;
+        P.n = n;
+        P.first_pixel = o->first_pixel;
+        P.tag_stride = o->tag_stride;
+        P.tag_offset = o->tag_offset;
+        P.sample = o->sample;
+        launch_camera(P, query_grid(path_resident_blocks(), n), stream);
+        return RT_OK;
+    });
 }
 
 rt_status compact_paths(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
-                        uint32_t stream_count, uint32_t* index, uint32_t* count, hipStream_t stream, bool own_stream) {
+                        uint32_t stream_count, uint32_t* index, uint32_t* count, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (rt_status st = validate_compact(c, paths, n, mask, streams, stream_count, index, count)) return st;
     if (n == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;   // no geometry is read
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    QuerySlot& q = *qp;
-    // The slot's own storage: its previous query has been harvested, so nothing reads what a growth
-    // frees.  Grown to the largest size any compaction asked for, so the slots stop growing together.
-    const size_t need = compact_scratch_bytes(n);
-    c->q_scratch_max = std::max(c->q_scratch_max, need);
-    if (q.scratch.bytes < need)
-        if (rt_status st = dev_alloc(c, q.scratch, c->q_scratch_max)) return st;
-    CompactParams P;
-    std::memset(&P, 0, sizeof P);
-    P.paths = (const float4*)paths;
-    for (uint32_t k = 0; k < stream_count; ++k) {
-        P.src[k] = (const float4*)streams[k].src;
-        P.dst[k] = (float4*)streams[k].dst;
-        P.words[k] = streams[k].words;
-    }
-    P.index = index;
-    P.count = count;
-    P.tiles = compact_tiles(n);
-    P.bits = (unsigned long long*)q.scratch.p;
-    P.tile_count = (uint32_t*)(P.bits + (size_t)P.tiles * kCompactSegs);
-    P.n = n;
-    P.mask = mask;
-    P.streams = stream_count;
-    launch_compact(P, std::min(path_resident_blocks(), P.tiles), stream);
-    HIPC(c, hipGetLastError());
-    return commit_query(c, q, stream, true);
+    return enqueue_query(c, where, false, [&](QuerySlot& q, const Geo&, hipStream_t stream) -> rt_status {
+        // The slot's own storage: its previous query has been harvested, so nothing reads what a growth
+        // frees.  Grown to the largest size any compaction asked for, so the slots stop growing together.
+        const size_t need = compact_scratch_bytes(n);
+        c->q_scratch_max = std::max(c->q_scratch_max, need);
+        if (q.scratch.bytes < need)
+            if (rt_status st = dev_alloc(c, q.scratch, c->q_scratch_max)) return st;
+        CompactParams P;
+        std::memset(&P, 0, sizeof P);
+        P.paths = (const float4*)paths;
+        for (uint32_t k = 0; k < stream_count; ++k) {
+            P.src[k] = (const float4*)streams[k].src;
+            P.dst[k] = (float4*)streams[k].dst;
+            P.words[k] = streams[k].words;
+        }
+        P.index = index;
+        P.count = count;
+        P.tiles = compact_tiles(n);
+        P.bits = (unsigned long long*)q.scratch.p;
+        P.tile_count = (uint32_t*)(P.bits + (size_t)P.tiles * kCompactSegs);
+        P.n = n;
+        P.mask = mask;
+        P.streams = stream_count;
+        launch_compact(P, std::min(path_resident_blocks(), P.tiles), stream);   // one block per tile at the most
+        return RT_OK;
+    });
 }
 
 rt_status connect_paths(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
-                        const uint32_t* occluded, uint32_t m, hipStream_t stream, bool own_stream) {
+                        const uint32_t* occluded, uint32_t m, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (m > 0 && n > 0) {
         if (!paths || !contrib || !occluded) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
@@ -297,34 +303,28 @@ rt_status connect_paths(rt_ctx* c, rt_path* paths, uint32_t n, const float* cont
             FAIL(c, RT_ERR_INVALID_ARG, "paths and contrib must be 16-byte aligned, index and occluded 4-byte aligned");
     }
     if (m == 0 || n == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    const ConnectParams P{(float4*)paths, (const float4*)contrib, index, occluded, n, m};
-    launch_connect(P, path_blocks(m), stream);
-    HIPC(c, hipGetLastError());
-    return commit_query(c, *qp, stream, true);
+    return enqueue_query(c, where, false, [&](QuerySlot&, const Geo&, hipStream_t stream) -> rt_status {
+        const ConnectParams P{(float4*)paths, (const float4*)contrib, index, occluded, n, m};
+        launch_connect(P, query_grid(path_resident_blocks(), m), stream);
+        return RT_OK;
+    });
 }
 
-rt_status retire_paths(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags, hipStream_t stream,
-                       bool own_stream) {
+rt_status retire_paths(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (n > 0 && tags > 0) {
         if (!paths || !samples) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
         if (((uintptr_t)paths | (uintptr_t)samples) & 15u) FAIL(c, RT_ERR_INVALID_ARG, "paths and samples must be 16-byte aligned");
     }
     if (n == 0 || tags == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    const RetireParams P{(const float4*)paths, (float4*)samples, n, tags};
-    launch_retire(P, path_blocks(n), stream);
-    HIPC(c, hipGetLastError());
-    return commit_query(c, *qp, stream, true);
+    return enqueue_query(c, where, false, [&](QuerySlot&, const Geo&, hipStream_t stream) -> rt_status {
+        const RetireParams P{(const float4*)paths, (float4*)samples, n, tags};
+        launch_retire(P, query_grid(path_resident_blocks(), n), stream);
+        return RT_OK;
+    });
 }
 
-rt_status average_samples(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba, hipStream_t stream,
-                          bool own_stream) {
+rt_status average_samples(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba, QueryStream where) {
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (spp < 1 || spp > 64) FAIL(c, RT_ERR_INVALID_ARG, "spp outside 1 .. 64");
     if (pixels > 0) {
@@ -333,13 +333,11 @@ rt_status average_samples(rt_ctx* c, const float* samples, uint32_t pixels, uint
         if (samples == rgba) FAIL(c, RT_ERR_INVALID_ARG, "in place is not supported");
     }
     if (pixels == 0) return RT_OK;
-    QuerySlot* qp = nullptr;
-    const Geo* gp = nullptr;
-    if (rt_status st = begin_query(c, stream, own_stream, qp, gp)) return st;
-    const AverageParams P{(const float4*)samples, (float4*)rgba, pixels, spp};
-    launch_average(P, path_blocks(pixels), stream);
-    HIPC(c, hipGetLastError());
-    return commit_query(c, *qp, stream, true);
+    return enqueue_query(c, where, false, [&](QuerySlot&, const Geo&, hipStream_t stream) -> rt_status {
+        const AverageParams P{(const float4*)samples, (float4*)rgba, pixels, spp};
+        launch_average(P, query_grid(path_resident_blocks(), pixels), stream);
+        return RT_OK;
+    });
 }
 }  // namespace
 
@@ -352,88 +350,89 @@ rt_status drain_queries(rt_ctx* c) {
 extern "C" {
 
 rt_status rt_trace_closest(rt_ctx* c, const rt_ray* rays, uint32_t n, rt_ray_hit* hits) {
-    return trace(c, rays, n, hits, false, nullptr, true);
+    return trace(c, rays, n, hits, false, QueryStream::of_ctx());
 }
 
 rt_status rt_trace_any(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t* occluded) {
-    return trace(c, rays, n, occluded, true, nullptr, true);
+    return trace(c, rays, n, occluded, true, QueryStream::of_ctx());
 }
 
 rt_status rt_trace_closest_on(rt_ctx* c, const rt_ray* rays, uint32_t n, rt_ray_hit* hits, void* stream) {
-    return trace(c, rays, n, hits, false, (hipStream_t)stream, false);
+    return trace(c, rays, n, hits, false, QueryStream::on(stream));
 }
 
 rt_status rt_trace_any_on(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t* occluded, void* stream) {
-    return trace(c, rays, n, occluded, true, (hipStream_t)stream, false);
+    return trace(c, rays, n, occluded, true, QueryStream::on(stream));
 }
 
 rt_status rt_resolve_hits(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
                           rt_surface_material* materials) {
-    return resolve(c, rays, hits, n, surfaces, materials, nullptr, true);
+    return resolve(c, rays, hits, n, surfaces, materials, QueryStream::of_ctx());
 }
 
 rt_status rt_resolve_hits_on(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
                              rt_surface_material* materials, void* stream) {
-    return resolve(c, rays, hits, n, surfaces, materials, (hipStream_t)stream, false);
+    return resolve(c, rays, hits, n, surfaces, materials, QueryStream::on(stream));
 }
 
 rt_status rt_shade_hits(rt_ctx* c, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
                         const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths,
                         rt_ray* next_rays, rt_ray* shadow_rays, float* contrib) {
-    return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib, nullptr, true);
+    return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib,
+                 QueryStream::of_ctx());
 }
 
 rt_status rt_shade_hits_on(rt_ctx* c, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
                            const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths,
                            rt_ray* next_rays, rt_ray* shadow_rays, float* contrib, void* stream) {
     return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib,
-                 (hipStream_t)stream, false);
+                 QueryStream::on(stream));
 }
 
 rt_status rt_camera_paths(rt_ctx* c, const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
                           uint32_t n, rt_ray* rays, rt_path* paths) {
-    return camera_paths(c, u, opts, random_offsets, n, rays, paths, nullptr, true);
+    return camera_paths(c, u, opts, random_offsets, n, rays, paths, QueryStream::of_ctx());
 }
 
 rt_status rt_camera_paths_on(rt_ctx* c, const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
                              uint32_t n, rt_ray* rays, rt_path* paths, void* stream) {
-    return camera_paths(c, u, opts, random_offsets, n, rays, paths, (hipStream_t)stream, false);
+    return camera_paths(c, u, opts, random_offsets, n, rays, paths, QueryStream::on(stream));
 }
 
 rt_status rt_compact_paths(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
                            uint32_t stream_count, uint32_t* index, uint32_t* count) {
-    return compact_paths(c, paths, n, mask, streams, stream_count, index, count, nullptr, true);
+    return compact_paths(c, paths, n, mask, streams, stream_count, index, count, QueryStream::of_ctx());
 }
 
 rt_status rt_compact_paths_on(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
                               uint32_t stream_count, uint32_t* index, uint32_t* count, void* stream) {
-    return compact_paths(c, paths, n, mask, streams, stream_count, index, count, (hipStream_t)stream, false);
+    return compact_paths(c, paths, n, mask, streams, stream_count, index, count, QueryStream::on(stream));
 }
 
 rt_status rt_connect_paths(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
                            const uint32_t* occluded, uint32_t m) {
-    return connect_paths(c, paths, n, contrib, index, occluded, m, nullptr, true);
+    return connect_paths(c, paths, n, contrib, index, occluded, m, QueryStream::of_ctx());
 }
 
 rt_status rt_connect_paths_on(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
                               const uint32_t* occluded, uint32_t m, void* stream) {
-    return connect_paths(c, paths, n, contrib, index, occluded, m, (hipStream_t)stream, false);
+    return connect_paths(c, paths, n, contrib, index, occluded, m, QueryStream::on(stream));
 }
 
 rt_status rt_retire_paths(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags) {
-    return retire_paths(c, paths, n, samples, tags, nullptr, true);
+    return retire_paths(c, paths, n, samples, tags, QueryStream::of_ctx());
 }
 
 rt_status rt_retire_paths_on(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags, void* stream) {
-    return retire_paths(c, paths, n, samples, tags, (hipStream_t)stream, false);
+    return retire_paths(c, paths, n, samples, tags, QueryStream::on(stream));
 }
 
 rt_status rt_average_samples(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba) {
-    return average_samples(c, samples, pixels, spp, rgba, nullptr, true);
+    return average_samples(c, samples, pixels, spp, rgba, QueryStream::of_ctx());
 }
 
 rt_status rt_average_samples_on(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba, void* stream) {
-    return average_samples(c, samples, pixels, spp, rgba, (hipStream_t)stream, false);
+    return average_samples(c, samples, pixels, spp, rgba, QueryStream::on(stream));
 }
 
 rt_status rt_get_query_stats(rt_ctx* c, rt_query_stats* out) {

@@ -74,7 +74,7 @@ struct QuerySlot {
     rt::Pinned<unsigned long long> h_counters;
     rt::Event ev0, ev1, done;   // around the launch (timing); after the counters' copy
     bool pending = false, any = false;
-    bool resolve = false;       // rt_resolve_hits took the slot: only `done` is used, nothing is folded
+    bool counted = false;       // a trace: folded into rt_query_stats; every other query uses `done` only
     uint32_t blocks = 0;        // the launch's grid
 };
 

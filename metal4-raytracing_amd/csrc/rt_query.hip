@@ -352,18 +352,22 @@ __global__ void __launch_bounds__(kBlock) rq_compact_copy(CompactParams P) {
     }
 }
 
-}  // namespace
-
-unsigned path_resident_blocks() {
+// Blocks of kBlock threads of `Kernel` the chip holds at once (CUs x blocks per CU; 256 x 4 where
+// the runtime does not say), found once per process and kernel.
+// The cache takes the device that is current at first use.
+template <auto Kernel>
+unsigned resident_blocks() {
     static const unsigned resident = [] {
         int dev = 0, cus = 256, per = 0;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        // the kernel that holds the most LDS: one figure serves all
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rq_compact_copy, kBlock, 0) != hipSuccess || per < 1) per = 4;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, Kernel, kBlock, 0) != hipSuccess || per < 1) per = 4;
         return (unsigned)(cus * per);
     }();
     return resident;
 }
+}  // namespace
+
+unsigned path_resident_blocks() { return resident_blocks<&rq_compact_copy>(); }   // the kernel that holds the most LDS: one figure serves all
 
 void launch_camera(const CamParams& P, unsigned blocks, hipStream_t stream) {
     hipLaunchKernelGGL(rq_camera, dim3(blocks), dim3(kBlock), 0, stream, P);
@@ -383,32 +387,14 @@ void launch_compact(const CompactParams& P, unsigned tile_blocks, hipStream_t st
     hipLaunchKernelGGL(rq_compact_copy, dim3(tile_blocks), dim3(kBlock), 0, stream, P);
 }
 
-unsigned shade_resident_blocks() {
-    static const unsigned resident = [] {
-        int dev = 0, cus = 256, per = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rq_shade<false>, kBlock, 0) != hipSuccess || per < 1) per = 4;
-        return (unsigned)(cus * per);
-    }();
-    return resident;
-}
+unsigned shade_resident_blocks() { return resident_blocks<&rq_shade<false>>(); }
 
 void launch_shade(const ShParams& P, unsigned blocks, hipStream_t stream) {
     auto kernel = P.randoms ? rq_shade<true> : rq_shade<false>;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, P);
 }
 
-unsigned resolve_resident_blocks() {
-    static const unsigned resident = [] {
-        int dev = 0, cus = 256, per = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        // the variant that holds the most registers: one figure serves all four
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rq_resolve<true, true>, kBlock, 0) != hipSuccess || per < 1)
-            per = 4;
-        return (unsigned)(cus * per);
-    }();
-    return resident;
-}
+unsigned resolve_resident_blocks() { return resident_blocks<&rq_resolve<true, true>>(); }   // the variant that holds the most registers: one figure serves all four
 
 void launch_resolve(const DevScene& S, const RsParams& P, unsigned blocks, hipStream_t stream) {
     const bool mat = P.materials != nullptr, tex = S.textured != 0;
@@ -417,16 +403,7 @@ void launch_resolve(const DevScene& S, const RsParams& P, unsigned blocks, hipSt
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, S, P);
 }
 
-unsigned query_resident_blocks() {
-    static const unsigned resident = [] {
-        int dev = 0, cus = 256, per = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rq_trace<false, false>, kBlock, 0) != hipSuccess || per < 1)
-            per = 4;
-        return (unsigned)(cus * per);
-    }();
-    return resident;
-}
+unsigned query_resident_blocks() { return resident_blocks<&rq_trace<false, false>>(); }
 
 void launch_query(const DevScene& S, const RqParams& Q, bool any, bool count, unsigned blocks, hipStream_t stream) {
     auto kernel = any ? (count ? rq_trace<true, true> : rq_trace<true, false>)

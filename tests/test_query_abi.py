@@ -64,6 +64,28 @@ def test_query_null_arguments_return_status(rt):
     assert lib.rt_last_error(None)   # message set, no crash
 
 
+def test_on_twins_and_query_module(rt):
+    """Every `_on` entry point is its plain form plus a trailing stream handle, and the package's
+    query names are the queries submodule's."""
+    import importlib
+    lib, A = rt.lib(), rt._abi
+    assert len(A.ON_TWINS) == len(set(A.ON_TWINS)) == 11
+    for name in A.ON_TWINS:
+        plain, on = getattr(lib, name), getattr(lib, name + "_on")
+        assert on.argtypes == plain.argtypes + [C.c_void_p], name
+        assert on.restype == plain.restype, name
+        assert name in A.EXPORTED_SYMBOLS and name + "_on" in A.EXPORTED_SYMBOLS, name
+    assert sorted(n[:-3] for n in A.EXPORTED_SYMBOLS if n.endswith("_on")) == sorted(A.ON_TWINS)
+    Q = importlib.import_module(rt.__name__ + ".queries")
+    for name in ("Hits", "Surface", "Paths", "Shaded", "Compacted", "debug_trace_host", "debug_resolve_host",
+                 "debug_shade_host", "debug_camera_paths_host"):
+        assert getattr(rt, name) is getattr(Q, name), name
+    assert issubclass(rt.Renderer, Q.RendererQueries)
+    for name in ("make_rays", "trace", "resolve", "make_paths", "shade", "camera_paths", "compact", "connect", "retire",
+                 "average", "_path_buffers", "path_trace", "query_stats"):
+        assert callable(getattr(rt.Renderer, name)) and name in vars(Q.RendererQueries), name
+
+
 def test_make_rays_host_layout(rt):
     o = np.array([[1, 2, 3], [4, 5, 6]], np.float32)
     d = np.array([[0, 0, 1], [0, 2, 0]], np.float32)
