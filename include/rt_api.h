@@ -222,6 +222,11 @@ typedef struct rt_stats {
     uint64_t total_auto_rebuilds;
     float bvh_cost_built;
     float bvh_cost_refit;
+    /* closest-hit rays their producer retired: the exact boxes of the BVH root's children proved a
+       miss (root mask 0), so the ray was never enqueued.  They count in closest_rays, trace_rays and
+       trace_closest_rays as the misses wf_trace would have resolved.  Last frame; running total. */
+    uint64_t root_retired_rays;
+    uint64_t total_root_retired_rays;
 } rt_stats;
 
 rt_status rt_create(const rt_opts* opts, rt_ctx** out);

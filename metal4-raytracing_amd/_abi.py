@@ -193,6 +193,8 @@ class Stats(C.Structure):
         ("total_auto_rebuilds", C.c_uint64),
         ("bvh_cost_built", C.c_float),
         ("bvh_cost_refit", C.c_float),
+        ("root_retired_rays", C.c_uint64),
+        ("total_root_retired_rays", C.c_uint64),
     ]
 
 

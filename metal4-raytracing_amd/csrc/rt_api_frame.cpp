@@ -144,21 +144,23 @@ rt_status harvest(rt_ctx* c, int k) {
     if (!f.wavefront) S.kernel_ms[0] = ms;
     S.pipeline = f.wavefront ? RT_PIPELINE_WAVEFRONT : RT_PIPELINE_MEGAKERNEL;
     S.iterations = w.iterations;
-    S.trace_rays = w.trace_rays;
-    S.trace_launches = w.trace_launches;
-    S.trace_ms = w.trace_ms;
-    S.trace_dev_ms = w.trace_dev_ms;
-    S.trace_dev_launches = w.trace_dev_launches;
-    S.finish_dev_ms = w.finish_dev_ms;
-    S.finish_dev_launches = w.finish_dev_launches;
-    S.trace_closest_rays = w.trace_closest_rays;
-    S.finish_launches = w.finish_launches;
     const unsigned long long* hc = f.h_counters.get();
     auto total = [hc](int word) {
         unsigned long long t = 0;
         for (int r = 0; r < kCntReplicas; ++r) t += hc[cnt_word(word, r)];
         return t;
     };
+    // rays a producer retired on root mask 0 count as traced: the misses wf_trace would have resolved
+    S.root_retired_rays = f.wavefront ? total(kCntRootRetired) : 0;
+    S.trace_rays = w.trace_rays + S.root_retired_rays;
+    S.trace_launches = w.trace_launches;
+    S.trace_ms = w.trace_ms;
+    S.trace_dev_ms = w.trace_dev_ms;
+    S.trace_dev_launches = w.trace_dev_launches;
+    S.finish_dev_ms = w.finish_dev_ms;
+    S.finish_dev_launches = w.finish_dev_launches;
+    S.trace_closest_rays = w.trace_closest_rays + S.root_retired_rays;
+    S.finish_launches = w.finish_launches;
     S.closest_rays = total(kCntClosest);
     S.shadow_rays = total(kCntShadow);
     S.node_visits = total(kCntNodes);
@@ -176,6 +178,7 @@ rt_status harvest(rt_ctx* c, int k) {
     for (int i = 0; i < 7; ++i) S.total_kernel_ms[i] += S.kernel_ms[i];
     S.total_trace_rays += S.trace_rays;
     S.total_trace_closest_rays += S.trace_closest_rays;
+    S.total_root_retired_rays += S.root_retired_rays;
     S.total_trace_ms += S.trace_ms;
     S.total_trace_launches += (uint64_t)S.trace_launches;
     S.total_trace_dev_ms += S.trace_dev_ms;
@@ -198,6 +201,7 @@ DevScene device_scene(const rt_ctx* c, const Geo& geo) {
     std::memset(&S, 0, sizeof S);   // no stray padding bytes: the frame-graph key compares S byte for byte
     S.tris = (const float*)geo[Geo::tris].p;
     S.nodes8 = (const Bvh8Node*)geo[Geo::nodes].p;
+    S.root_box = (const RootBoxes*)geo[Geo::root_box].p;
     S.tri_info = (const uint4*)c->d_tri_info.p;
     S.pos = (const float4*)geo[Geo::pos].p;
     S.prev_pos = (const float4*)geo[Geo::prev_pos].p;

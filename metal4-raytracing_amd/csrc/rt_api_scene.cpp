@@ -122,6 +122,17 @@ rt_status upload_skinning(rt_ctx* c, const rt_scene_desc* sd) {
 
 // The node-area sum of the current generation's tree (launch_bvh_cost) on the update stream: read
 // back at once (sync = true, after a build) or into the pinned word with an event (after a refit).
+// The exact boxes of the root's children (launch_root_boxes) of the current generation's tree, on the
+// update stream: after the tree's upload, the device build and every refit.
+rt_status root_boxes(rt_ctx* c) {
+    Geo& g = c->G();
+    if (rt_status st = dev_alloc(c, g[Geo::root_box], sizeof(RootBoxes))) return st;
+    launch_root_boxes((const Bvh8Node*)g[Geo::nodes].p, (const float*)g[Geo::node_box].p, (const float*)g[Geo::tris].p,
+                      (RootBoxes*)g[Geo::root_box].p, c->ustream);
+    HIPC(c, hipGetLastError());
+    return RT_OK;
+}
+
 rt_status bvh_cost(rt_ctx* c, bool sync) {
     if (rt_status st = dev_alloc(c, c->d_cost, 4)) return st;
     if (!c->h_cost) HIPC(c, c->h_cost.alloc(16));
@@ -273,6 +284,7 @@ rt_status rt_bvh_build(rt_ctx* c) {
     for (uint32_t k = 0; k < n; ++k) tri_bin[c->bvh8.tri_order[k]] = (uint16_t)(((uint64_t)k * kSortMaxBins) / n);
     if ((st = dev_upload(c, g[Geo::tri_bin], tri_bin.data(), (size_t)n * 2, us))) return st;
     c->num_nodes8 = (uint32_t)nn;
+    if ((st = root_boxes(c))) return st;
     if ((st = bvh_cost(c, true))) return st;
     HIPC(c, hipStreamSynchronize(us));   // the host arrays are the copies' sources
     g.num_nodes8 = (uint32_t)nn;
@@ -319,6 +331,7 @@ rt_status rt_bvh_build_device(rt_ctx* c) {
     launch_flatten((const uint4*)c->d_tri_info.p, (const uint32_t*)c->d_slot_to_tri.p, (const float4*)g[Geo::pos].p,
                    (const float*)g[Geo::inst].p, (float*)g[Geo::tris].p, n, (unsigned*)c->d_maxabs.p, us);
     HIPC(c, hipGetLastError());
+    if ((st = root_boxes(c))) return st;
     HIPC(c, hipStreamSynchronize(us));
     if (res.num_nodes >= (1u << 23)) FAIL(c, RT_ERR_UNSUPPORTED, "BVH too large (2^23 nodes)");
     c->level_off = res.level_off;
@@ -353,6 +366,7 @@ rt_status rt_bvh_refit(rt_ctx* c) {
                             c->ustream);
     }
     HIPC(c, hipGetLastError());
+    if ((st = root_boxes(c))) return st;
     // the refitted tree's node-area sum, read back without a host wait (check_refit_quality)
     if (refit_rebuild_pct(c) > 0) return bvh_cost(c, false);
     return RT_OK;

@@ -55,7 +55,7 @@ struct FrameSlot {
 // copy per generation (rt::FrameRing; Renderer.swift keeps per-frame position buffers for the same
 // reason, :1290-1303).  A new buffer is a new name before kCount.
 struct Geo {
-    enum Buf { pos, prev_pos, nrm, inst, prev_inst, tris, nodes, node_box, tri_bin, tri_nrm, kCount };
+    enum Buf { pos, prev_pos, nrm, inst, prev_inst, tris, nodes, node_box, tri_bin, tri_nrm, root_box, kCount };
     rt::DevBuf buf[kCount];
     uint32_t num_nodes8 = 0;
     rt::DevBuf& operator[](Buf b) { return buf[b]; }

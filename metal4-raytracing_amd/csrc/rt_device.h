@@ -22,9 +22,11 @@ namespace rt {
 constexpr int kStackSize = 16;   // per-thread traversal stack entries (LDS): node groups of the 8-wide BVH
 constexpr int kBlock = 256;      // threads per block for the traversal kernels
 
+struct RootBoxes;
 struct DevScene {
     const float* tris;   // 16 floats per slot (kTriFloats)
     const Bvh8Node* nodes8;
+    const RootBoxes* root_box;   // fp32 bounds of the root's eight child slots (root_word_tight)
     const uint4* tri_info;
     const float4* pos;
     const float4* prev_pos;
@@ -260,6 +262,108 @@ __host__ __device__ __forceinline__ uint32_t root_word(const NodeWords& root, f3
     return 0u;
 #endif
 }
+// ---- exact root boxes ----------------------------------------------------------------------------
+// The root's 8-bit grid spans the whole scene, so a flat child (a floor: exactly y = 0) is stored as
+// a slab one grid step thick, and a ray that starts 1e-3 off that floor and leaves it still "hits"
+// it.  RootBoxes holds the fp32 bounds of the root's eight child slots instead, one per geometry
+// generation (DevScene::root_box; root_boxes_fill after every build and refit), and
+// root_word_tight is root_word on those planes: the same slab values, bounds and min / max
+// structure as node8_hit_slots, the planes read as they are (no byte conversion).  A producer
+// whose closest-hit ray gets mask 0 has proven a miss and does not enqueue it.  RT_ROOT_TIGHT=0
+// (A/B builds): producers hand on root_word's quantised masks and retire nothing.
+#ifndef RT_ROOT_TIGHT
+#define RT_ROOT_TIGHT 1
+#endif
+struct RootBoxes {
+    float b[3][2][8];   // [axis][0: lo, 1: hi][slot]: a lane picks its near / far planes by address
+    uint32_t used;      // bit c: slot c holds a child (an empty slot's box is inverted: +inf .. -inf)
+    uint32_t reserved[3];
+};
+static_assert(sizeof(RootBoxes) == 208, "RootBoxes: 48 planes and the used word, 16-B rows");
+
+// Bounds of the root's child slot c before padding: an internal child's stored box (node_box, 6
+// floats per node), a leaf's from its <= 4 triangle records.  False for an empty slot.
+__host__ __device__ __forceinline__ bool root_child_bounds(const Bvh8Node* nodes, const float* node_box, const float* tris,
+                                                           int c, float lo[3], float hi[3]) {
+    const Bvh8Node& nd = nodes[0];
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = INFINITY;
+        hi[a] = -INFINITY;
+    }
+    if (nd.q[c] == 255 && nd.q[8 + c] == 0) return false;   // unused: qlo = 255 > qhi = 0 on x
+    const int k_int = nd.axis_k >> 4;
+    if (c < k_int) {
+        const float* bx = node_box + 6 * (size_t)(nd.child_base + (uint32_t)c);
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = bx[a];
+            hi[a] = bx[3 + a];
+        }
+    } else {
+        const int j = c - k_int;
+        const uint32_t first = nd.tri_base + bvh8_leaf_first(nd.tri_valid, j), n = bvh8_leaf_count(nd.tri_valid, j);
+        for (uint32_t t = 0; t < n; ++t)
+            for (int q = 0; q < 3; ++q) {
+                const f3 v = tri_vertex(tri_rec(tris, first + t), q);
+                lo[0] = fminf(lo[0], v.x); hi[0] = fmaxf(hi[0], v.x);
+                lo[1] = fminf(lo[1], v.y); hi[1] = fmaxf(hi[1], v.y);
+                lo[2] = fminf(lo[2], v.z); hi[2] = fmaxf(hi[2], v.z);
+            }
+        if (n == 0) return false;
+    }
+    return true;
+}
+// The pad of axis a: 2^-19 of the root box's largest |coordinate| on that axis (the
+// slab test on the padded planes passes whenever the watertight triangle test can).
+constexpr float kRootPadRel = 1.0f / 524288.0f;
+// Slot c of the boxes from its bounds and the per-axis pads.
+__host__ __device__ __forceinline__ void root_box_store(RootBoxes& B, int c, bool used, const float lo[3], const float hi[3],
+                                                        const float pad[3]) {
+    for (int a = 0; a < 3; ++a) {
+        B.b[a][0][c] = used ? lo[a] - pad[a] : INFINITY;
+        B.b[a][1][c] = used ? hi[a] + pad[a] : -INFINITY;
+    }
+}
+// All of it, serially (host tools; the device fills one slot per lane: root_boxes_k, rt_util.hip).
+__host__ __device__ inline void root_boxes_fill(RootBoxes& B, const Bvh8Node* nodes, const float* node_box, const float* tris) {
+    float lo[8][3], hi[8][3], m[3] = {0.0f, 0.0f, 0.0f};
+    bool used[8];
+    for (int c = 0; c < 8; ++c) {
+        used[c] = root_child_bounds(nodes, node_box, tris, c, lo[c], hi[c]);
+        for (int a = 0; a < 3; ++a)
+            if (used[c]) m[a] = fmaxf(m[a], fmaxf(fabsf(lo[c][a]), fabsf(hi[c][a])));
+    }
+    const float pad[3] = {kRootPadRel * m[0], kRootPadRel * m[1], kRootPadRel * m[2]};
+    B.used = 0u;
+    B.reserved[0] = B.reserved[1] = B.reserved[2] = 0u;
+    for (int c = 0; c < 8; ++c) {
+        root_box_store(B, c, used[c], lo[c], hi[c], pad);
+        B.used |= used[c] ? 1u << c : 0u;
+    }
+}
+
+__host__ __device__ __forceinline__ uint32_t root_word_tight(const RootBoxes& B, f3 o, f3 d, float tmax) {
+    const RaySetup R = ray_setup(o, d);   // only the slab part is read: the exact divisions are dead code
+    // near / far planes by direction sign: rows of eight, picked by address
+    const float* nx = B.b[0][R.ix >= 0.0f ? 0 : 1];
+    const float* fx = B.b[0][R.ix >= 0.0f ? 1 : 0];
+    const float* ny = B.b[1][R.iy >= 0.0f ? 0 : 1];
+    const float* fy = B.b[1][R.iy >= 0.0f ? 1 : 0];
+    const float* nz = B.b[2][R.iz >= 0.0f ? 0 : 1];
+    const float* fz = B.b[2][R.iz >= 0.0f ? 1 : 0];
+    const float tmin = 0.0f, tf_max = tmax * 1.0000004f;
+    uint32_t hm = 0;
+    #pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float tnx = __builtin_fmaf(nx[c], R.ix, -R.ox), tfx = __builtin_fmaf(fx[c], R.ix, -R.ox);
+        const float tny = __builtin_fmaf(ny[c], R.iy, -R.oy), tfy = __builtin_fmaf(fy[c], R.iy, -R.oy);
+        const float tnz = __builtin_fmaf(nz[c], R.iz, -R.oz), tfz = __builtin_fmaf(fz[c], R.iz, -R.oz);
+        const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
+        const float tf = fminf(fminf(tfx, tfy), fminf(tfz, tf_max));
+        hm |= tn <= tf ? (1u << c) : 0u;
+    }
+    return kRootValid | (hm & B.used);
+}
+
 // The root's header words as the consumer keeps them (uniform: read once per launch).
 struct RootHead {
     uint32_t ew;

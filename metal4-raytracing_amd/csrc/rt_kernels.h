@@ -11,11 +11,12 @@ namespace rt {
 
 constexpr int kHaltonLds = 64;   // first Halton dimensions staged in LDS per block
 
-// kCntNodes: every node test.  Slots 8 and 9 are unused (formerly LDS-served node tests).
+// kCntNodes: every node test.  Slot 9 is unused (formerly LDS-served node tests).
 // kCntTrace*: the share of the visits made by wf_trace launches.
+// kCntRootRetired: closest-hit rays their producer retired on root mask 0 (also in kCntClosest).
 enum CounterSlot {
     kCntClosest = 0, kCntShadow = 1, kCntNodes = 2, kCntTris = 3, kCntPaths = 4, kCntOverflow = 5,
-    kCntTraceNodes = 6, kCntTraceTris = 7, kCntSlots = 10
+    kCntTraceNodes = 6, kCntTraceTris = 7, kCntRootRetired = 8, kCntSlots = 10
 };
 
 struct FrameParams {
@@ -54,12 +55,13 @@ __host__ __device__ constexpr uint32_t cnt_word(int slot, int rep) {
 // trace_kernel: the node / triangle visits are also added to the kCntTrace* slots.
 __device__ __forceinline__ void block_flush_counters(unsigned long long* counters, uint32_t closest, uint32_t shadow,
                                                      uint32_t nodes, uint32_t tris, uint32_t paths, bool overflow,
-                                                     bool trace_kernel = false, uint32_t lds_nodes = 0) {
+                                                     bool trace_kernel = false, uint32_t lds_nodes = 0,
+                                                     uint32_t root_retired = 0) {
     __shared__ unsigned long long red[kBlock / 64][kCntSlots];
     const unsigned long long l = wave_sum(lds_nodes), n = wave_sum(nodes) + l, t = wave_sum(tris);
     const unsigned long long v[kCntSlots] = {wave_sum(closest), wave_sum(shadow), n, t, wave_sum(paths),
                                              __ballot(overflow) != 0ull ? 1ull : 0ull,
-                                             trace_kernel ? n : 0ull, trace_kernel ? t : 0ull, l,
+                                             trace_kernel ? n : 0ull, trace_kernel ? t : 0ull, wave_sum(root_retired),
                                              trace_kernel ? l : 0ull};
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
@@ -245,6 +247,8 @@ void launch_flatten(const uint4* tri_info, const uint32_t* slot_to_tri, const fl
 // per-triangle shading records of triangles [t0, t0 + n) (DevScene::tri_nrm) from tri_info and the
 // vertex normals; rebuilt whenever normals change (scene upload, skinning)
 void launch_tri_nrm(const uint4* tri_info, const float4* nrm, float4* tri_nrm, uint32_t t0, uint32_t n, hipStream_t s);
+// the fp32 bounds of the root's eight child slots (rt_device.h RootBoxes) from the tree as it stands
+void launch_root_boxes(const Bvh8Node* nodes, const float* node_box, const float* tris, RootBoxes* out, hipStream_t s);
 // pad = max(pad_min, 4e-6 * max |coordinate|) as the builder pads (rt_bvh.cpp)
 void launch_refit8_level(Bvh8Node* nodes, float* node_box, const float* tris, const uint32_t* level_nodes,
                          uint32_t count, float pad_min, const unsigned* maxabs_bits, hipStream_t s);

@@ -269,4 +269,29 @@ void launch_refit8_level(Bvh8Node* nodes, float* node_box, const float* tris, co
                        count, pad_min, maxabs_bits);
 }
 
+// ---- exact root boxes (rt_device.h RootBoxes): one block, lane c fills child slot c ----------------
+// After the tree's upload, the device build and every refit (after the root's level), on the update
+// stream: one code path for all three.
+__global__ void __launch_bounds__(64) root_boxes_k(const Bvh8Node* __restrict__ nodes, const float* __restrict__ node_box,
+                                                   const float* __restrict__ tris, RootBoxes* __restrict__ out) {
+    const int c = (int)threadIdx.x & 7;   // lanes 8.. repeat the slots: the reductions below stay full-wave
+    float lo[3], hi[3], pad[3];
+    const bool used = root_child_bounds(nodes, node_box, tris, c, lo, hi);
+    for (int a = 0; a < 3; ++a) {
+        float m = used ? fmaxf(fabsf(lo[a]), fabsf(hi[a])) : 0.0f;
+        #pragma unroll
+        for (int off = 4; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        pad[a] = kRootPadRel * m;
+    }
+    const uint32_t mask = (uint32_t)(__ballot(used) & 0xffull);
+    if (threadIdx.x < 8) root_box_store(*out, c, used, lo, hi, pad);
+    if (threadIdx.x == 0) {
+        out->used = mask;
+        out->reserved[0] = out->reserved[1] = out->reserved[2] = 0u;
+    }
+}
+void launch_root_boxes(const Bvh8Node* nodes, const float* node_box, const float* tris, RootBoxes* out, hipStream_t s) {
+    hipLaunchKernelGGL(root_boxes_k, dim3(1), dim3(64), 0, s, nodes, node_box, tris, out);
+}
+
 }  // namespace rt

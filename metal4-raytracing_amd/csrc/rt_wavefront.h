@@ -136,6 +136,7 @@ struct WfParams {
     int spans;             // record device-clock launch spans (rt_set_device_spans)
     int dev_ctl;           // device-side control (enqueue_frame): kernels read their queue sizes from
                            // the counters and skip once the live count fell below `tail`
+    int count;             // the frame runs the counting instances: producers count a retired ray's root visit
     int finish_q;          // dev_ctl: the finish queue when every enqueued bulk round ran (written by generate)
     const FrameParams* Pd; // this frame's FrameParams in device memory (W.d_params)
     PixelMap px;           // path id -> own pixel -> image pixel (own_pixel, rt_wf_queue.h)

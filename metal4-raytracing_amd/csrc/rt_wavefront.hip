@@ -3,12 +3,14 @@
 // The per-pixel loop of raytracingKernel (Raytracing.metal:269-790) is split into stages over
 // SoA path state and compacted queues, so every wave64 works on live paths only:
 //   generate  one thread per (own pixel, sample): primary ray (:270-292) -> ray queue, with the
-//             ray's root word (the BVH root's 8-wide test, root_word)
+//             ray's root word (the BVH root's 8-wide test on the exact boxes of its children,
+//             root_word_tight); a ray that misses them all is a proven miss and is not enqueued
 //   extend    closest-hit traversal of the ray queue (:314-322)          -> hit records; a ray
 //             with a root word starts at the root's result (trav_start_root), one step later
 //   shade     shade_step per hit (:324-774): updates path state, appends the continuation
 //             ray to the next queue and the NEE shadow ray to the shadow queue, each with its
-//             root word; a block first compacts the hits of its queue entries, so a missed ray
+//             root word (a continuation ray with root mask 0 is not appended: its path ends as
+//             after a miss); a block first compacts the hits of its queue entries, so a missed ray
 //             takes no lane
 //   connect   any-hit traversal of the shadow queue (:716-743); unoccluded -> accum += contrib;
 //             starts from the shadow ray's root word as extend does
@@ -80,9 +82,17 @@ __device__ __forceinline__ void init_path(const WfParams& Q, uint32_t pid, uint3
 
 __device__ __forceinline__ void flush_counters(const FrameParams& P, uint32_t closest, uint32_t shadow, uint32_t paths,
                                                const TraceCounters& tc, bool count, bool overflow,
-                                               bool trace_kernel = false) {
+                                               bool trace_kernel = false, uint32_t root_retired = 0) {
     block_flush_counters(P.counters, closest, shadow, count ? tc.nodes : 0u, count ? tc.tris : 0u, paths, overflow,
-                         trace_kernel, count ? tc.lds_nodes : 0u);
+                         trace_kernel, count ? tc.lds_nodes : 0u, root_retired);
+}
+// A producer's end: the closest-hit rays it retired on root mask 0 (`retired`, a wave-uniform count)
+// count where wf_trace would have counted them as misses: closest rays, and in a counting frame one
+// node visit each (the root) of the traversal launches.
+__device__ __forceinline__ void flush_producer(const FrameParams& P, const WfParams& Q, uint32_t retired, uint32_t paths) {
+    const uint32_t r = lane_id() == 0 ? retired : 0u;
+    const TraceCounters tc{r, 0, 0};
+    flush_counters(P, r, 0, paths, tc, Q.count != 0, false, true, r);
 }
 
 // per-pixel outputs of a shade step (depth / motion / G-buffer, :342-389, :506-515)
@@ -100,14 +110,30 @@ __device__ __forceinline__ void write_pixel_outputs(const FrameParams& P, uint32
 }
 
 // ---- root words (rt_device.h root_word, rt_trav.h trav_start_root) -------------------------------
-// Producers: the root's five words once per block into LDS (call before a block barrier that comes
-// before the first root_word, such as load_tabs'); the mask then costs no memory access per ray.
-__device__ __forceinline__ void stage_root(const DevScene& S, NodeWords* lds_root) {
+// Producers: what their root test reads, once per block into LDS (call before a block barrier that
+// comes before the first producer_root_word, such as load_tabs'); the mask then costs no memory
+// access per ray.  RT_ROOT_TIGHT: the exact boxes of the root's children; else the root's five words.
+#if RT_ROOT_TIGHT
+using RootLds = RootBoxes;
+#else
+using RootLds = NodeWords;
+#endif
+__device__ __forceinline__ void stage_root(const DevScene& S, RootLds* lds_root) {
     static_assert(sizeof(NodeWords) == sizeof(Bvh8Node) && offsetof(NodeWords, h1) == 16 && offsetof(NodeWords, qx) == 32,
                   "NodeWords: the node's own layout");
-    if (threadIdx.x < sizeof(Bvh8Node) / 4u)
-        reinterpret_cast<uint32_t*>(lds_root)[threadIdx.x] = reinterpret_cast<const uint32_t*>(S.nodes8)[threadIdx.x];
+    const uint32_t* src = RT_ROOT_TIGHT ? reinterpret_cast<const uint32_t*>(S.root_box) : reinterpret_cast<const uint32_t*>(S.nodes8);
+    if (threadIdx.x < sizeof(RootLds) / 4u) reinterpret_cast<uint32_t*>(lds_root)[threadIdx.x] = src[threadIdx.x];
 }
+__device__ __forceinline__ uint32_t producer_root_word(const RootLds& root, f3 o, f3 d, float tmax) {
+#if RT_ROOT_TIGHT
+    return root_word_tight(root, o, d, tmax);
+#else
+    return root_word(root, o, d, tmax);
+#endif
+}
+// A closest-hit ray its producer retires: a valid word with mask 0 is a proven miss (its first
+// trav_step would return one), so the ray is not enqueued and its path ends here.
+__device__ __forceinline__ bool root_retires(uint32_t word) { return RT_ROOT_TIGHT && word == kRootValid; }
 // Consumers: the root's header words, the same for every lane (scalar registers).
 __device__ __forceinline__ RootHead load_root_head(const DevScene& S) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(S.nodes8);
@@ -204,7 +230,7 @@ __global__ void __launch_bounds__(kBlock) wf_generate(DevScene S, const FramePar
     const FrameParams& P = *Pp;   // per-frame parameters in device memory
     __shared__ HaltonDim lds_halton[kHaltonLds];
     __shared__ BlockAlloc ba;
-    __shared__ NodeWords lds_root;
+    __shared__ RootLds lds_root;
     stage_root(S, &lds_root);
     const ShadeTabs halton = load_tabs(S, lds_halton, nullptr);   // no shading: Halton only
     const Uniforms& U = P.U;
@@ -212,7 +238,7 @@ __global__ void __launch_bounds__(kBlock) wf_generate(DevScene S, const FramePar
     const int shard = blockIdx.x & (kShards - 1);
     float4* qout = Q.W.q[0] + 2 * (size_t)shard * Q.seg_cap;
     uint32_t* qrout = Q.W.qr[0] + (size_t)shard * Q.seg_cap;
-    uint32_t n_paths = 0;
+    uint32_t n_paths = 0, n_retired = 0;   // n_retired: wave-uniform
     const uint32_t total = Q.base_paths;
     if (Q.dev_ctl && blockIdx.x == 0 && threadIdx.x == 0) Q.W.counts[cslot(kCntFinishQ)] = (uint32_t)Q.finish_q;
     for (uint32_t base = blockIdx.x * kBlock; base < total; base += gridDim.x * kBlock) {
@@ -227,15 +253,19 @@ __global__ void __launch_bounds__(kBlock) wf_generate(DevScene S, const FramePar
             n_paths++;
         }
         bool live = valid && U.maxBounces > 0;
+        // the primary ray's root word; a ray that leaves the scene is never enqueued
+        const uint32_t rw = live ? producer_root_word(lds_root, o, d, INFINITY) : 0u;
+        const bool dead = live && root_retires(rw);
+        n_retired += (uint32_t)__popcll(__ballot(dead));
+        live = live && !dead;
         uint32_t slot = block_alloc(live, &Q.W.counts[cslot(shard)], ba);
         if (live) {
             qout[2 * slot] = make_float4(o.x, o.y, o.z, __uint_as_float(pid));
             qout[2 * slot + 1] = make_float4(d.x, d.y, d.z, 0.0f);
-            qrout[slot] = root_word(lds_root, o, d, INFINITY);
+            qrout[slot] = rw;
         }
     }
-    TraceCounters tc{0, 0, 0};
-    flush_counters(P, 0, 0, n_paths, tc, false, false);
+    flush_producer(P, Q, n_retired, n_paths);
 }
 
 // ---- shade -------------------------------------------------------------------------------------------
@@ -251,7 +281,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
     __shared__ float4 lds_inst[3 * kInstLds];
     __shared__ Light lds_light[kLightLds];
     __shared__ BlockAllocOct bao;
-    __shared__ NodeWords lds_root;
+    __shared__ RootLds lds_root;
     if (tail_mode(Q)) return;
     stage_root(S, &lds_root);
     const ShadeTabs halton = load_tabs(S, lds_halton, lds_mat, lds_inst, lds_light, P.U.lightCount);
@@ -295,6 +325,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
     __shared__ float4 ring_h[SORTED ? 1 : kRing];
     __shared__ uint32_t ring_w[2][kBlock / 64];   // the waves' hit counts of a fill (double-buffered: one barrier per fill)
     uint32_t head = 0, pending = 0, fills = 0;    // block-uniform
+    uint32_t n_retired = 0;                       // wave-uniform: continuation rays retired on root mask 0
     uint32_t base = beg;
     while (true) {
         uint32_t g = base + threadIdx.x;
@@ -395,6 +426,13 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
                 }
             }
         }
+        // each ray with its root word: the root's 8-wide test here, at this kernel's lane
+        // utilisation, and the traversal starts from its result (trav_start_root).  A continuation
+        // ray that leaves the scene is never enqueued: its path ends as after a miss record.
+        const uint32_t rwn = r.next ? producer_root_word(lds_root, rayO, rayD, INFINITY) : 0u;
+        const bool dead = r.next && root_retires(rwn);
+        n_retired += (uint32_t)__popcll(__ballot(dead));
+        r.next = r.next && !dead;
         const bool pr[3] = {r.shadow, r.next && front, r.next && !front};
         uint32_t* const ctr[3] = {&Q.W.counts[cslot(kCntShadowQ + shard)], &Q.W.counts[cslot(next * kShards + shard)],
                                   &Q.W.counts[cslot(kCntBack + next * kShards + shard)]};
@@ -403,21 +441,20 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
         const uint32_t oct = (rayD.x < 0.0f ? 1u : 0u) | (rayD.y < 0.0f ? 2u : 0u) | (rayD.z < 0.0f ? 4u : 0u);
         block_alloc3_oct(pr, oct, ctr, bao, slots);
         const uint32_t ns = slots[0], nr = front ? slots[1] : Q.seg_cap - 1u - slots[2];
-        // each ray with its root word: the root's 8-wide test here, at this kernel's lane
-        // utilisation, and the traversal starts from its result (trav_start_root)
         if (r.shadow) {
             sqout[3 * (size_t)ns] = make_float4(r.so.x, r.so.y, r.so.z, __uint_as_float(pid));
             sqout[3 * (size_t)ns + 1] = make_float4(r.sd.x, r.sd.y, r.sd.z, r.stmax);
             sqout[3 * (size_t)ns + 2] = make_float4(r.contrib.x, r.contrib.y, r.contrib.z,
-                                                    __uint_as_float(root_word(lds_root, r.so, r.sd, r.stmax)));
+                                                    __uint_as_float(producer_root_word(lds_root, r.so, r.sd, r.stmax)));
         }
         if (r.next) {
             qout[2 * (size_t)nr] = make_float4(rayO.x, rayO.y, rayO.z, __uint_as_float(pid));
             qout[2 * (size_t)nr + 1] = make_float4(rayD.x, rayD.y, rayD.z, __uint_as_float(nstate));
             qcout[nr] = ncol;
-            qrout[nr] = root_word(lds_root, rayO, rayD, INFINITY);
+            qrout[nr] = rwn;
         }
     }
+    flush_producer(P, Q, n_retired, 0);
 }
 
 // ---- hit sort (between extend and shade) -------------------------------------------------------------

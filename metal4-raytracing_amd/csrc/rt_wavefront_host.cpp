@@ -513,6 +513,7 @@ bool run_wavefront(const DevScene& S, const FrameParams& P, WavefrontBuffers& W,
     Q.fchunk = tu.fchunk;
     Q.shade_blocks = tu.shade_blocks;
     Q.spans = spans ? 1 : 0;
+    Q.count = count ? 1 : 0;
     Q.px.spp_div = make_fastdiv((uint32_t)Q.spp);
     Q.px.tile = P.tile_size;
     Q.px.rank = P.rank;

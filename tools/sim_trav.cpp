@@ -62,14 +62,25 @@ struct Policy {
                             // rt_trav.h trav_start_root): its first step is the root's triangles or first
                             // child.  The producer's cost is not in this model (wf_shade / wf_generate run
                             // the same ~194-issue test at their own, higher lane utilisation).
+    int root_tight = 0;     // with root_known: the producer tested the exact fp32 boxes of the root's children
+                            // (rt_device.h RootBoxes, root_word_tight: true bounds, the 2^-19 pad rule)
+    int retire = 0;         // with root_tight: a ray whose tight mask is 0 is never enqueued (its producer
+                            // retires it); it still counts as a ray in the per-ray figures
 };
 
 struct Scene8 {
     std::vector<Bvh8Node> nodes;
     std::vector<float4> tris;   // 3 per slot
+    RootBoxes boxes;            // the exact boxes of the root's children (policy "tight root")
 };
 
-static void start(Lane& L, const Ray& r, const Bvh8Node* nodes = nullptr, bool root_known = false) {
+// the tight root word's mask of a ray (closest hit: tmax = infinity)
+static uint32_t tight_mask(const Scene8& S, const Ray& r, float tmax = INFINITY) {
+    return root_word_tight(S.boxes, r.o, r.d, tmax) & 0xffu;
+}
+
+static void start(Lane& L, const Ray& r, const Bvh8Node* nodes = nullptr, bool root_known = false,
+                  const RootBoxes* tight = nullptr) {
     L.R = ray_setup(r.o, r.d);
     L.o = r.o;
     L.best = INFINITY;
@@ -85,6 +96,11 @@ static void start(Lane& L, const Ray& r, const Bvh8Node* nodes = nullptr, bool r
     L.steps = 0;
     if (root_known) {   // the state the root's node step leaves; a ray that misses the root ends in its first step
         test_node8(nodes, 0u, L.R, 0.0f, L.best, L.g_hits, L.t_mask, L.t_valid, L.g_base, L.t_base, L.g_flip);
+        if (tight) {   // the same decode from the exact boxes' mask
+            const NodeWords W = load_node8(nodes, 0u);
+            node8_decode(root_word_tight(*tight, r.o, r.d, INFINITY) & 0xffu, __builtin_bit_cast(uint32_t, W.h0.w), W.h1, L.R.dneg,
+                         L.g_hits, L.t_mask, L.t_valid, L.g_base, L.t_base, L.g_flip);
+        }
         L.t_pair = nodes[0].reserved;
     }
 }
@@ -204,8 +220,16 @@ struct Result {
     double blk_iss[5] = {}, blk_lanes[5] = {};   // head, refill, tri (all k), node, stack
 };
 
-static Result simulate(const Scene8& S, const std::vector<Ray>& rays, const Policy& P) {
+static Result simulate(const Scene8& S, const std::vector<Ray>& all_rays, const Policy& P) {
     Result res;
+    // retired rays never reach the queue; they count as rays that cost the traversal nothing
+    std::vector<Ray> kept;
+    if (P.retire) {
+        for (const Ray& r : all_rays)
+            if (tight_mask(S, r)) kept.push_back(r);
+        res.rays += (double)(all_rays.size() - kept.size());
+    }
+    const std::vector<Ray>& rays = P.retire ? kept : all_rays;
     const int W = 64;
     size_t next = 0;
     const size_t chunk = 64;
@@ -232,7 +256,7 @@ static Result simulate(const Scene8& S, const std::vector<Ray>& rays, const Poli
                 int got = 0;
                 for (auto& L : lanes)
                     if (!L.active && wnext[w] < wend[w]) {
-                        start(L, rays[wnext[w]], S.nodes.data(), P.root_known != 0);
+                        start(L, rays[wnext[w]], S.nodes.data(), P.root_known != 0, P.root_tight ? &S.boxes : nullptr);
                         L.ray = (int)wnext[w];
                         ++wnext[w];
                         ++got;
@@ -393,6 +417,10 @@ int main(int argc, char** argv) {
         }
     }
     fprintf(stderr, "%zu nodes, depth %d\n", S.nodes.size(), b8.max_depth);
+    std::vector<float> recs((size_t)kTriFloats * b8.tri_order.size());   // the product's 64-B records (trace8, root boxes)
+    for (size_t k = 0; k < b8.tri_order.size(); ++k)
+        tri_store(&recs[(size_t)kTriFloats * k], &world[9 * (size_t)b8.tri_order[k]], b8.tri_order[k]);
+    root_boxes_fill(S.boxes, S.nodes.data(), b8.node_box.data(), recs.data());
     for (int ni = 0; ni < 3; ++ni) {
         const Bvh8Node& r = S.nodes[ni];
         fprintf(stderr, "node %d: k_int %d tri_base %u tri_valid %08x\n", ni, r.axis_k >> 4, r.tri_base, r.tri_valid);
@@ -414,11 +442,11 @@ int main(int argc, char** argv) {
     TraceCounters tc{0, 0, 0};
     std::vector<int> stackbuf(16 * kBlock);
     DevScene DS{};
-    std::vector<float> recs((size_t)kTriFloats * b8.tri_order.size());   // the product's 64-B records for trace8
-    for (size_t k = 0; k < b8.tri_order.size(); ++k)
-        tri_store(&recs[(size_t)kTriFloats * k], &world[9 * (size_t)b8.tri_order[k]], b8.tri_order[k]);
     DS.tris = recs.data();
     DS.nodes8 = S.nodes.data();
+    struct Shadow { Ray r; float tmax; };
+    std::vector<Shadow> shadow;   // from the primary hits to light 0
+    const f3 light0 = D.light_count ? ldf3(D.lights[0].position) : mk3(0, 10, 0);
     for (const Ray& r : prim) {
         Hit h;
         bool ovf = false;
@@ -434,12 +462,45 @@ int main(int argc, char** argv) {
         f3 X = normalize(cross(t, N)), Y = cross(N, X);
         f3 d = normalize((X * (cosf(phi) * sr) + Y * (sinf(phi) * sr)) + N * sqrtf(1.0f - r2));
         sec.push_back(Ray{P + N * 1e-3f, d});
+        const f3 so = P + N * 1e-3f;
+        const float dist = length(light0 - so);
+        shadow.push_back(Shadow{Ray{so, (light0 - so) * (1.0f / dist)}, dist});
+    }
+    // what the exact root boxes change before any schedule: root masks of 0, root slots hit per ray, and
+    // (the check behind retiring) rays with a tight mask of 0 that nevertheless have a hit
+    {
+        const NodeWords rootw = load_node8(S.nodes.data(), 0u);
+        auto report = [&](const char* name, size_t nrays, auto ray_at, auto tmax_at, bool any) {
+            double zero_q = 0, zero_t = 0, slots_q = 0, slots_t = 0, miss = 0, bad = 0;
+            for (size_t i = 0; i < nrays; ++i) {
+                const Ray& r = ray_at(i);
+                const float tmax = tmax_at(i);
+                const uint32_t q = root_word(rootw, r.o, r.d, tmax) & 0xffu, t = tight_mask(S, r, tmax);
+                Hit h;
+                bool ovf = false;
+                const bool found = any ? trace8<true, false>(DS, r.o, r.d, 0.0f, tmax, h, stackbuf.data(), tc, ovf)
+                                       : trace8<false, false>(DS, r.o, r.d, 0.0f, tmax, h, stackbuf.data(), tc, ovf);
+                zero_q += q == 0u; zero_t += t == 0u;
+                slots_q += __builtin_popcount(q); slots_t += __builtin_popcount(t);
+                miss += !found;
+                bad += t == 0u && found;
+            }
+            printf("== root masks, %s rays (%zu): %.1f %% find nothing; mask 0: quantised %.1f %%, tight %.1f %%; "
+                   "root slots hit per ray: quantised %.2f, tight %.2f; tight mask 0 with a hit: %.0f\n",
+                   name, nrays, 100.0 * miss / nrays, 100.0 * zero_q / nrays, 100.0 * zero_t / nrays, slots_q / nrays,
+                   slots_t / nrays, bad);
+        };
+        report("primary", prim.size(), [&](size_t i) -> const Ray& { return prim[i]; }, [](size_t) { return INFINITY; }, false);
+        report("secondary", sec.size(), [&](size_t i) -> const Ray& { return sec[i]; }, [](size_t) { return INFINITY; }, false);
+        report("shadow", shadow.size(), [&](size_t i) -> const Ray& { return shadow[i].r; }, [&](size_t i) { return shadow[i].tmax; }, true);
     }
     fprintf(stderr, "%zu primary, %zu secondary rays\n", prim.size(), sec.size());
     std::vector<Policy> pols;
     pols.push_back(Policy{"current (refill 8, 2 tris)", 8, 2, 0});
     if (getenv("SIM_PAIRS")) pols.push_back(Policy{"edge-sharing pairs", 8, 2, 0, 0, 0, 1});
     pols.push_back(Policy{"root known (root word)", 8, 2, 0, 0, 0, 0, 1});
+    pols.push_back(Policy{"tight root", 8, 2, 0, 0, 0, 0, 1, 1, 0});
+    pols.push_back(Policy{"tight root, mask 0 retired", 8, 2, 0, 0, 0, 0, 1, 1, 1});
     pols.push_back(Policy{"refill 16", 16, 2, 0});
     pols.push_back(Policy{"1 tri per step", 8, 1, 0});
     pols.push_back(Policy{"4 tris per step", 8, 4, 0});
