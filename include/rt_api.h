@@ -227,6 +227,16 @@ typedef struct rt_stats {
        trace_closest_rays as the misses wf_trace would have resolved.  Last frame; running total. */
     uint64_t root_retired_rays;
     uint64_t total_root_retired_rays;
+    /* shadow rays a shading step resolved without a traversal; each counts in shadow_rays, and those
+       the wavefront's shade stage resolved in trace_rays, as the rays its connect launch would have
+       traced.  dark: the contribution is ±0 in every component, so the answer cannot change the
+       radiance (either pipeline).  root_unoccluded: the exact boxes of the BVH root's children
+       proved the ray unoccluded (root mask 0) and the shade stage added its contribution
+       (wavefront).  Last frame; running totals. */
+    uint64_t dark_shadow_rays;
+    uint64_t root_unoccluded_shadow_rays;
+    uint64_t total_dark_shadow_rays;
+    uint64_t total_root_unoccluded_shadow_rays;
 } rt_stats;
 
 rt_status rt_create(const rt_opts* opts, rt_ctx** out);

@@ -195,6 +195,10 @@ class Stats(C.Structure):
         ("bvh_cost_refit", C.c_float),
         ("root_retired_rays", C.c_uint64),
         ("total_root_retired_rays", C.c_uint64),
+        ("dark_shadow_rays", C.c_uint64),
+        ("root_unoccluded_shadow_rays", C.c_uint64),
+        ("total_dark_shadow_rays", C.c_uint64),
+        ("total_root_unoccluded_shadow_rays", C.c_uint64),
     ]
 
 

@@ -152,7 +152,11 @@ rt_status harvest(rt_ctx* c, int k) {
     };
     // rays a producer retired on root mask 0 count as traced: the misses wf_trace would have resolved
     S.root_retired_rays = f.wavefront ? total(kCntRootRetired) : 0;
-    S.trace_rays = w.trace_rays + S.root_retired_rays;
+    // shadow rays a shading step resolved itself; those of wf_shade count as traced, where connect
+    // would have counted them
+    S.dark_shadow_rays = total(kCntDarkShadow);
+    S.root_unoccluded_shadow_rays = f.wavefront ? total(kCntRootUnoccluded) : 0;
+    S.trace_rays = w.trace_rays + S.root_retired_rays + (f.wavefront ? total(kCntShadeSkipped) : 0);
     S.trace_launches = w.trace_launches;
     S.trace_ms = w.trace_ms;
     S.trace_dev_ms = w.trace_dev_ms;
@@ -179,6 +183,8 @@ rt_status harvest(rt_ctx* c, int k) {
     S.total_trace_rays += S.trace_rays;
     S.total_trace_closest_rays += S.trace_closest_rays;
     S.total_root_retired_rays += S.root_retired_rays;
+    S.total_dark_shadow_rays += S.dark_shadow_rays;
+    S.total_root_unoccluded_shadow_rays += S.root_unoccluded_shadow_rays;
     S.total_trace_ms += S.trace_ms;
     S.total_trace_launches += (uint64_t)S.trace_launches;
     S.total_trace_dev_ms += S.trace_dev_ms;

@@ -14,9 +14,15 @@ constexpr int kHaltonLds = 64;   // first Halton dimensions staged in LDS per bl
 // kCntNodes: every node test.  Slot 9 is unused (formerly LDS-served node tests).
 // kCntTrace*: the share of the visits made by wf_trace launches.
 // kCntRootRetired: closest-hit rays their producer retired on root mask 0 (also in kCntClosest).
+// Past kCntSlots, the shadow rays a shading step resolved without a traversal (flushed by the kernels
+// that shade: block_flush_counters<true>; each also in kCntShadow): kCntDarkShadow with a
+// contribution of ±0 (shadow_is_dark), kCntRootUnoccluded proven unoccluded by root mask 0;
+// kCntShadeSkipped: those of either class that wf_shade resolved, which a connect launch would
+// have traced.
 enum CounterSlot {
     kCntClosest = 0, kCntShadow = 1, kCntNodes = 2, kCntTris = 3, kCntPaths = 4, kCntOverflow = 5,
-    kCntTraceNodes = 6, kCntTraceTris = 7, kCntRootRetired = 8, kCntSlots = 10
+    kCntTraceNodes = 6, kCntTraceTris = 7, kCntRootRetired = 8, kCntSlots = 10,
+    kCntDarkShadow = 10, kCntRootUnoccluded = 11, kCntShadeSkipped = 12, kCntSlotsAll = 13
 };
 
 struct FrameParams {
@@ -45,7 +51,7 @@ __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
 // (device-scope atomics on one line serialise at ~88/us).  The host sums the replicas.
 constexpr int kCntReplicas = 8;
 constexpr int kCntLineU64 = 16;
-constexpr int kCounterWords = kCntSlots * kCntReplicas * kCntLineU64;
+constexpr int kCounterWords = kCntSlotsAll * kCntReplicas * kCntLineU64;
 __host__ __device__ constexpr uint32_t cnt_word(int slot, int rep) {
     return ((uint32_t)slot * kCntReplicas + (uint32_t)rep) * kCntLineU64;
 }
@@ -53,23 +59,30 @@ __host__ __device__ constexpr uint32_t cnt_word(int slot, int rep) {
 // Block-wide flush of the per-thread statistics; every thread of the block must call it.
 // nodes: global node fetches, lds_nodes: node tests served from LDS (both count as node visits).
 // trace_kernel: the node / triangle visits are also added to the kCntTrace* slots.
+// SKIPS (the kernels that shade): also the shadow rays their steps resolved without a traversal,
+// dark and root_unoccluded by class, shade_skipped those of both that wf_shade resolved.
+template <bool SKIPS = false>
 __device__ __forceinline__ void block_flush_counters(unsigned long long* counters, uint32_t closest, uint32_t shadow,
                                                      uint32_t nodes, uint32_t tris, uint32_t paths, bool overflow,
                                                      bool trace_kernel = false, uint32_t lds_nodes = 0,
-                                                     uint32_t root_retired = 0) {
-    __shared__ unsigned long long red[kBlock / 64][kCntSlots];
+                                                     uint32_t root_retired = 0, uint32_t dark = 0,
+                                                     uint32_t root_unoccluded = 0, uint32_t shade_skipped = 0) {
+    constexpr int kN = SKIPS ? kCntSlotsAll : kCntSlots;
+    __shared__ unsigned long long red[kBlock / 64][kN];
     const unsigned long long l = wave_sum(lds_nodes), n = wave_sum(nodes) + l, t = wave_sum(tris);
-    const unsigned long long v[kCntSlots] = {wave_sum(closest), wave_sum(shadow), n, t, wave_sum(paths),
-                                             __ballot(overflow) != 0ull ? 1ull : 0ull,
-                                             trace_kernel ? n : 0ull, trace_kernel ? t : 0ull, wave_sum(root_retired),
-                                             trace_kernel ? l : 0ull};
+    const unsigned long long v[kCntSlotsAll] = {wave_sum(closest), wave_sum(shadow), n, t, wave_sum(paths),
+                                                __ballot(overflow) != 0ull ? 1ull : 0ull,
+                                                trace_kernel ? n : 0ull, trace_kernel ? t : 0ull, wave_sum(root_retired),
+                                                trace_kernel ? l : 0ull,
+                                                SKIPS ? wave_sum(dark) : 0ull, SKIPS ? wave_sum(root_unoccluded) : 0ull,
+                                                SKIPS ? wave_sum(shade_skipped) : 0ull};
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         #pragma unroll
-        for (int k = 0; k < kCntSlots; ++k) red[wave][k] = v[k];
+        for (int k = 0; k < kN; ++k) red[wave][k] = v[k];
     }
     __syncthreads();
-    if (threadIdx.x < kCntSlots) {
+    if (threadIdx.x < kN) {
         unsigned long long s = 0;
         #pragma unroll
         for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];

@@ -35,7 +35,7 @@ megakernel(DevScene S, FrameParams P) {
 
     int* stack = &lds_stack[threadIdx.x];
     TraceCounters tc{0, 0, 0};
-    uint32_t n_closest = 0, n_shadow = 0, n_paths = 0;
+    uint32_t n_closest = 0, n_shadow = 0, n_paths = 0, n_dark = 0;
     bool overflow = false;
 
     if (px < U.width && py < U.height) {                                          // :241
@@ -93,6 +93,10 @@ megakernel(DevScene S, FrameParams P) {
                     if (!trace8<true, COUNT>(S, r.so, r.sd, 0.0f, r.stmax, sh, stack, tc, overflow))
                         p.accum = p.accum + r.contrib;
                 }
+                if (r.dark) {   // a contribution of ±0: counted, not traced (shade_step)
+                    n_shadow++;
+                    n_dark++;
+                }
                 if (!r.next) break;
             }
             totalColor = totalColor + p.accum;                                       // :777
@@ -111,7 +115,8 @@ megakernel(DevScene S, FrameParams P) {
             P.gbuffer[3 * plane + pix] = g3;
         }
     }
-    block_flush_counters(P.counters, n_closest, n_shadow, COUNT ? tc.nodes : 0u, COUNT ? tc.tris : 0u, n_paths, overflow);
+    block_flush_counters<true>(P.counters, n_closest, n_shadow, COUNT ? tc.nodes : 0u, COUNT ? tc.tris : 0u, n_paths, overflow,
+                               false, 0u, 0u, n_dark);
 }
 
 void launch_megakernel(const DevScene& S, const FrameParams& P, int nblocks, bool count, hipStream_t stream) {

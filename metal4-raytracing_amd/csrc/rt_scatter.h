@@ -39,10 +39,33 @@ RT_HD int scatter_light_index(float x, int count) {
     return v < (float)count ? (int)v : count - 1;
 }
 
+// What a spotlight pick needs of its record besides position and colour (:608-632): the normalised
+// cone axis and the cosine of the cone angle.  Pure functions of the record, so a draw policy may
+// hand out values it computed once (ShadeTabs, rt_shade.h: per block, where the lights are staged)
+// or compute them on the spot; either way by this one function, so the bits are the same.
+struct SpotCone {
+    f3 axis;
+    float cos_angle;
+};
+RT_HD SpotCone spot_cone(const Light& light) {
+    SpotCone c;
+    c.axis = normalize(ldf3(light.direction));
+    c.cos_angle = cos_pinned(light.coneAngle);
+    return c;
+}
+
+// A shadow ray whose answer cannot change the image: its contribution is ±0 in every component
+// (NdotL == 0 in PBR mode, which emits the ray whatever NdotL is, :692-744; or a zero colour
+// product), and accum is never -0, so accum + contrib has accum's bits whether the ray is occluded
+// or not.  False for NaN and for denormals.  The frame kernels do not trace such a ray
+// (shade_step, rt_shade.h); the queries still hand it to the caller, by their record rules.
+RT_HD bool shadow_is_dark(f3 contrib) { return contrib.x == 0.0f && contrib.y == 0.0f && contrib.z == 0.0f; }
+
 // Raytracing.metal:517-774 at surface point s with shading normal shadingNormal.  rayO / rayD (in:
 // the ray that hit; out: the next ray), color / accum, bounce / step / tpass are the renderer's
 // registers.  draws.draw(D, i, step) is random number D of step `step` of Halton index i,
-// draws.light(k) light record k; U carries shadingMode, maxBounces and lightCount.  Sets shadow
+// draws.light(k) light record k, draws.spot(k, light) its spot_cone; U carries shadingMode,
+// maxBounces and lightCount.  Sets shadow
 // and the shadow ray (so, sd, stmax) with its contribution when the step emits one, and leaves
 // them alone otherwise.  Returns whether the path goes on with rayO / rayD.
 template <class DRAWS, class OPTS>
@@ -110,7 +133,8 @@ RT_HD bool scatter_step(const DRAWS& draws, const OPTS& U, int hidx, const Surfa
     p.accum = p.accum + p.color * s.emission;                                         // :585
 
     float lightSample = draws.draw(kDrawLight, hidx, p.step);                         // :588-591
-    const Light& light = draws.light(scatter_light_index(lightSample, U.lightCount));
+    const int lightIndex = scatter_light_index(lightSample, U.lightCount);
+    const Light& light = draws.light(lightIndex);
     f3 Ldir, lightColor;
     float lightDistance;
     f3 lpos = ldf3(light.position), lcol = ldf3(light.color);
@@ -131,9 +155,9 @@ RT_HD bool scatter_step(const DRAWS& draws, const OPTS& U, int hidx, const Surfa
         float inv = 1.0f / fmaxf(lightDistance, 1e-3f);
         Ldir = Ldir * inv;
         lightColor = mk3(0.0f, 0.0f, 0.0f);
-        f3 coneDirection = normalize(ldf3(light.direction));
-        float spotResult = dot(-Ldir, coneDirection);
-        if (spotResult > cos_pinned(light.coneAngle)) lightColor = (lcol * inv) * inv;
+        const SpotCone cone = draws.spot(lightIndex, light);   // normalize(direction), cos(coneAngle)
+        float spotResult = dot(-Ldir, cone.axis);
+        if (spotResult > cone.cos_angle) lightColor = (lcol * inv) * inv;
     } else if (light.type == LightTypePointlight) {                                   // :633-638
         Ldir = lpos - s.P;
         lightDistance = length(Ldir);
@@ -230,6 +254,7 @@ struct QueryDraws {
         return halton_fast(i, tab[dim < (uint32_t)RT_HALTON_DIMS ? dim : (uint32_t)(RT_HALTON_DIMS - 1)]);
     }
     __host__ __device__ __forceinline__ const Light& light(int k) const { return lights[k]; }
+    __host__ __device__ __forceinline__ SpotCone spot(int, const Light& l) const { return spot_cone(l); }   // on the spot
 };
 
 // rt_path as 16-B words: (throughput, sample), (radiance, flags), (bounce, step, passes, reserved).

@@ -6,7 +6,9 @@
 // Given the current ray and its closest hit, shade_step updates the path registers (throughput
 // `color`, `accum`, bounce / step / transparencyPasses), optionally emits a shadow ray whose
 // contribution the caller adds to `accum` when it is unoccluded (Raytracing.metal:741-743 /
-// :667-669), and either rewrites the ray for the next iteration (next = true) or ends the path.
+// :667-669; a shadow ray whose contribution is ±0 is reported as `dark` instead and not traced:
+// shadow_is_dark, rt_scatter.h), and either rewrites the ray for the next iteration (next = true)
+// or ends the path.
 // The arithmetic is not stated here: shade_step fetches the hit's records from the block's LDS
 // tables (ShadeTabs), calls the surface half (surface_point / shading_normal, rt_surface.h) and
 // the scatter half (scatter_step, rt_scatter.h), the functions the device queries and the host
@@ -39,6 +41,8 @@ struct ShadeTabs {
     const Light* light_lds;
     const Light* light_glob;
     int n_light_lds;           // = lightCount when the lights fit in LDS, else 0
+    const SpotCone* spot_lds;  // spot_cone of every staged spotlight (load_tabs), beside its record
+    int n_spot_lds;            // = n_light_lds when the caller gave load_tabs an array for them, else 0
     __device__ __forceinline__ float operator()(int i, int d) const {
         if (d == 0) return halton_base2(i);   // base 2: closed form (bit-identical, rt_math.h)
         return halton_fast(i, d < kHaltonLds ? lds[d] : glob[d]);
@@ -60,14 +64,19 @@ struct ShadeTabs {
         return k < n_inst_lds ? reinterpret_cast<const float*>(inst_lds + 3 * k) : inst_glob + 12 * (size_t)k;
     }
     __device__ __forceinline__ const Light& light(int k) const { return k < n_light_lds ? light_lds[k] : light_glob[k]; }
+    // The spotlight's cone axis and cosine: ~80 VALU with an IEEE divide and a square root, and
+    // pure functions of the record, so a staged light has them from load_tabs (once per block, not
+    // once per hit that picks it); a light that is not staged computes them here, as before.
+    __device__ __forceinline__ SpotCone spot(int k, const Light& l) const { return k < n_spot_lds ? spot_lds[k] : spot_cone(l); }
 };
 
 // Stages the Halton dimensions and the material records, instance matrices and lights of the
-// scene in LDS (each table only when its LDS array is given and the scene's table fits); every
-// thread of the block calls it (ends with a barrier).
+// scene in LDS (each table only when its LDS array is given and the scene's table fits; with
+// lds_spot, also the spot_cone of each staged spotlight); every thread of the block calls it (ends
+// with a barrier).
 __device__ __forceinline__ ShadeTabs load_tabs(const DevScene& S, HaltonDim* lds_halton, MatRec* lds_mat,
                                                float4* lds_inst = nullptr, Light* lds_light = nullptr,
-                                               int light_count = 0) {
+                                               SpotCone* lds_spot = nullptr, int light_count = 0) {
     for (int i = threadIdx.x; i < kHaltonLds; i += blockDim.x) lds_halton[i] = S.halton[i];
     const int n_mat = (lds_mat && S.num_materials <= kMatLds) ? S.num_materials : 0;
     for (int i = threadIdx.x; i < n_mat; i += blockDim.x) {
@@ -80,15 +89,21 @@ __device__ __forceinline__ ShadeTabs load_tabs(const DevScene& S, HaltonDim* lds
     const float4* ig = reinterpret_cast<const float4*>(S.inst);
     for (int i = threadIdx.x; i < 3 * n_inst; i += blockDim.x) lds_inst[i] = ig[i];
     const int n_light = (lds_light && light_count <= kLightLds) ? light_count : 0;
-    for (int i = threadIdx.x; i < n_light; i += blockDim.x) lds_light[i] = S.lights[i];
+    for (int i = threadIdx.x; i < n_light; i += blockDim.x) {
+        const Light l = S.lights[i];
+        lds_light[i] = l;
+        if (lds_spot && l.type == LightTypeSpotlight) lds_spot[i] = spot_cone(l);   // read for spotlights only
+    }
     __syncthreads();
     return ShadeTabs{lds_halton, S.halton, lds_mat, S.materials, n_mat, lds_inst, S.inst, n_inst,
-                     lds_light, S.lights, n_light};
+                     lds_light, S.lights, n_light, lds_spot, lds_spot ? n_light : 0};
 }
 
 struct StepResult {
     bool next;             // trace rayO/rayD again
     bool shadow;           // trace shadow ray; add contrib to accum when unoccluded
+    bool dark;             // the step made a shadow ray that is not to be traced (shadow_is_dark): shadow is
+                           // clear and the path goes on as after an occluded one; it still counts as a shadow ray
     f3 so, sd, contrib;
     float stmax;
     bool primary;          // bounce 0 / sample 0 hit: depth + motion (:342-389)
@@ -151,6 +166,7 @@ __device__ __forceinline__ void shade_step(const DevScene& S, const Uniforms& U,
                                            StepResult& r) {
     r.next = false;
     r.shadow = false;
+    r.dark = false;
     r.primary = false;
     r.gbuf = false;
     const float4* const rec = S.tri_nrm + 4 * (size_t)h.id;   // (n1 | ti.w, n2, n0, ti)
@@ -211,6 +227,9 @@ __device__ __forceinline__ void shade_step(const DevScene& S, const Uniforms& U,
     }
 
     r.next = scatter_step(tabs, U, hidx, s, shadingNormal, rayO, rayD, p, r.shadow, r.so, r.sd, r.stmax, r.contrib);   // :517-774
+    // a contribution of ±0 leaves accum's bits alone whatever the ray finds (:741-743): not traced
+    r.dark = r.shadow && shadow_is_dark(r.contrib);
+    r.shadow = r.shadow && !r.dark;
 }
 
 // Primary ray for (pixel, sample) (Raytracing.metal:270-292).

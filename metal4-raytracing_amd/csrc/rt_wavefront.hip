@@ -10,8 +10,10 @@
 //   shade     shade_step per hit (:324-774): updates path state, appends the continuation
 //             ray to the next queue and the NEE shadow ray to the shadow queue, each with its
 //             root word (a continuation ray with root mask 0 is not appended: its path ends as
-//             after a miss); a block first compacts the hits of its queue entries, so a missed ray
-//             takes no lane
+//             after a miss; a shadow ray with root mask 0 is not appended either: it is proven
+//             unoccluded and shade adds its contribution itself; nor is a dark one, whose
+//             contribution of ±0 cannot change accum, shade_step); a block first compacts the hits
+//             of its queue entries, so a missed ray takes no lane
 //   connect   any-hit traversal of the shadow queue (:716-743); unoccluded -> accum += contrib;
 //             starts from the shadow ray's root word as extend does
 //   finish    once fewer than kTailRays paths are alive, one launch runs every remaining path
@@ -23,7 +25,8 @@
 //
 // Results are bit-identical to the megakernel: per-path arithmetic is the same shade_step,
 // the accumulation order per path is the reference's (emission of step s, then its shadow
-// contribution, then step s+1), and samples are summed per pixel in sample order.
+// contribution -- added by connect, or by shade for a ray it proved unoccluded -- then step s+1),
+// and samples are summed per pixel in sample order.
 //
 // This file holds the kernels only: the sharded queues and the index maths are rt_wf_queue.h, the
 // stepwise traversal rt_trav.h, the counter words rt_wf_counters.h; rt_wavefront_host.cpp launches
@@ -80,19 +83,27 @@ __device__ __forceinline__ void init_path(const WfParams& Q, uint32_t pid, uint3
 }
 
 
+// SKIPS: a kernel that shades, with the shadow rays its steps resolved themselves (rt_kernels.h)
+template <bool SKIPS = false>
 __device__ __forceinline__ void flush_counters(const FrameParams& P, uint32_t closest, uint32_t shadow, uint32_t paths,
                                                const TraceCounters& tc, bool count, bool overflow,
-                                               bool trace_kernel = false, uint32_t root_retired = 0) {
-    block_flush_counters(P.counters, closest, shadow, count ? tc.nodes : 0u, count ? tc.tris : 0u, paths, overflow,
-                         trace_kernel, count ? tc.lds_nodes : 0u, root_retired);
+                                               bool trace_kernel = false, uint32_t root_retired = 0, uint32_t dark = 0,
+                                               uint32_t root_unoccluded = 0, uint32_t shade_skipped = 0) {
+    block_flush_counters<SKIPS>(P.counters, closest, shadow, count ? tc.nodes : 0u, count ? tc.tris : 0u, paths, overflow,
+                                trace_kernel, count ? tc.lds_nodes : 0u, root_retired, dark, root_unoccluded, shade_skipped);
 }
 // A producer's end: the closest-hit rays it retired on root mask 0 (`retired`, a wave-uniform count)
 // count where wf_trace would have counted them as misses: closest rays, and in a counting frame one
-// node visit each (the root) of the traversal launches.
-__device__ __forceinline__ void flush_producer(const FrameParams& P, const WfParams& Q, uint32_t retired, uint32_t paths) {
-    const uint32_t r = lane_id() == 0 ? retired : 0u;
+// node visit each (the root) of the traversal launches.  The shadow rays wf_shade resolved itself
+// (`dark`, `unoccluded`: wave-uniform counts by class) count where connect would have counted
+// them, as shadow rays; they add no node visit and no triangle test, since none happens.
+template <bool SKIPS = false>
+__device__ __forceinline__ void flush_producer(const FrameParams& P, const WfParams& Q, uint32_t retired, uint32_t paths,
+                                               uint32_t dark = 0, uint32_t unoccluded = 0) {
+    const bool l0 = lane_id() == 0;
+    const uint32_t r = l0 ? retired : 0u, dk = l0 ? dark : 0u, un = l0 ? unoccluded : 0u;
     const TraceCounters tc{r, 0, 0};
-    flush_counters(P, r, 0, paths, tc, Q.count != 0, false, true, r);
+    flush_counters<SKIPS>(P, r, dk + un, paths, tc, Q.count != 0, false, true, r, dk, un, dk + un);
 }
 
 // per-pixel outputs of a shade step (depth / motion / G-buffer, :342-389, :506-515)
@@ -134,6 +145,12 @@ __device__ __forceinline__ uint32_t producer_root_word(const RootLds& root, f3 o
 // A closest-hit ray its producer retires: a valid word with mask 0 is a proven miss (its first
 // trav_step would return one), so the ray is not enqueued and its path ends here.
 __device__ __forceinline__ bool root_retires(uint32_t word) { return RT_ROOT_TIGHT && word == kRootValid; }
+// A shadow ray wf_shade resolves: the same word proves it unoccluded (connect's first trav_step would
+// end it with no hit), so wf_shade adds its contribution itself and appends no shadow entry.
+#ifndef RT_SHADE_UNOCCLUDED
+#define RT_SHADE_UNOCCLUDED RT_ROOT_TIGHT   // 0: such a ray keeps its shadow entry and connect ends it in one iteration
+#endif
+__device__ __forceinline__ bool root_unoccluded(uint32_t word) { return RT_SHADE_UNOCCLUDED && word == kRootValid; }
 // Consumers: the root's header words, the same for every lane (scalar registers).
 __device__ __forceinline__ RootHead load_root_head(const DevScene& S) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(S.nodes8);
@@ -273,18 +290,22 @@ __global__ void __launch_bounds__(kBlock) wf_generate(DevScene S, const FramePar
 // blocks of XCD k (blockIdx % 8) shade the k-th eighth of it, so one XCD's L2 serves one scene
 // region and the rays / shadow rays it appends to its queue shard stay grouped by region for
 // the next extend / connect launches (which hand shard k's range to XCD k).
+// The radiance instances are held at five waves per SIMD (96 VGPRs): left to itself the compiler takes
+// 102 for <false, false> and drops to four.
 template <bool FULL, bool SORTED>
-__global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur) {
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FULL ? 3 : 5, FULL ? 3 : 5)))
+wf_shade(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int cur) {
     const FrameParams& P = *Pp;   // per-frame parameters in device memory
     __shared__ HaltonDim lds_halton[kHaltonLds];
     __shared__ MatRec lds_mat[kMatLds];
     __shared__ float4 lds_inst[3 * kInstLds];
     __shared__ Light lds_light[kLightLds];
+    __shared__ SpotCone lds_spot[kLightLds];
     __shared__ BlockAllocOct bao;
     __shared__ RootLds lds_root;
     if (tail_mode(Q)) return;
     stage_root(S, &lds_root);
-    const ShadeTabs halton = load_tabs(S, lds_halton, lds_mat, lds_inst, lds_light, P.U.lightCount);
+    const ShadeTabs halton = load_tabs(S, lds_halton, lds_mat, lds_inst, lds_light, lds_spot, P.U.lightCount);
     const Uniforms& U = P.U;
     const int next = 1 - cur;
     const int shard = blockIdx.x & (kShards - 1);
@@ -326,6 +347,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
     __shared__ uint32_t ring_w[2][kBlock / 64];   // the waves' hit counts of a fill (double-buffered: one barrier per fill)
     uint32_t head = 0, pending = 0, fills = 0;    // block-uniform
     uint32_t n_retired = 0;                       // wave-uniform: continuation rays retired on root mask 0
+    uint32_t n_dark = 0, n_unoccluded = 0;        // wave-uniform: shadow rays resolved here (±0 contribution; root mask 0)
     uint32_t base = beg;
     while (true) {
         uint32_t g = base + threadIdx.x;
@@ -371,6 +393,9 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
         StepResult r;
         r.next = false;
         r.shadow = false;
+        r.dark = false;
+        bool lit = false;               // the step's shadow ray is proven unoccluded (root mask 0)
+        uint32_t rws = 0;               // the shadow ray's root word
         uint32_t pid = 0, nstate = 0;   // nstate, ncol: the continuation's state bits and colour
         bool front = true;              // the continuation goes to the queue front (likely_long)
         f3 rayO = mk3(0, 0, 0), rayD = mk3(0, 0, 0);
@@ -415,13 +440,21 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
                 nstate = pack_state(p.bounce, p.tpass, p.step);
                 front = likely_long(p);
                 ncol = make_float4(p.color.x, p.color.y, p.color.z, __uint_as_float(meta.w));   // w: Halton index
-                // radiance only changes on emissive hits (:585-586): skip the store otherwise
-                if (__float_as_uint(p.accum.x) != __float_as_uint(a.x) || __float_as_uint(p.accum.y) != __float_as_uint(a.y) ||
+                // A shadow ray with root mask 0 is proven unoccluded: its contribution is added here,
+                // in connect's order (:741-743 after :585: (stored + emission) + contribution), and
+                // it gets no shadow entry.  (A dark one has neither: shade_step cleared r.shadow.)
+                rws = r.shadow ? producer_root_word(lds_root, r.so, r.sd, r.stmax) : 0u;
+                lit = r.shadow && root_unoccluded(rws);
+                r.shadow = r.shadow && !lit;
+                // radiance only changes on emissive hits (:585-586) and by such a contribution: skip
+                // the read and the store otherwise (no emission: s + (+0) == s, s is never -0)
+                if (lit || __float_as_uint(p.accum.x) != __float_as_uint(a.x) || __float_as_uint(p.accum.y) != __float_as_uint(a.y) ||
                     __float_as_uint(p.accum.z) != __float_as_uint(a.z)) {
                     if (!FULL) {
                         const float4 s = Q.W.p_accum[pid];
                         p.accum = mk3(s.x + p.accum.x, s.y + p.accum.y, s.z + p.accum.z);
                     }
+                    if (lit) p.accum = p.accum + r.contrib;
                     Q.W.p_accum[pid] = make_float4(p.accum.x, p.accum.y, p.accum.z, 0.0f);
                 }
             }
@@ -433,6 +466,8 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
         const bool dead = r.next && root_retires(rwn);
         n_retired += (uint32_t)__popcll(__ballot(dead));
         r.next = r.next && !dead;
+        n_dark += (uint32_t)__popcll(__ballot(r.dark));
+        n_unoccluded += (uint32_t)__popcll(__ballot(lit));
         const bool pr[3] = {r.shadow, r.next && front, r.next && !front};
         uint32_t* const ctr[3] = {&Q.W.counts[cslot(kCntShadowQ + shard)], &Q.W.counts[cslot(next * kShards + shard)],
                                   &Q.W.counts[cslot(kCntBack + next * kShards + shard)]};
@@ -444,8 +479,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
         if (r.shadow) {
             sqout[3 * (size_t)ns] = make_float4(r.so.x, r.so.y, r.so.z, __uint_as_float(pid));
             sqout[3 * (size_t)ns + 1] = make_float4(r.sd.x, r.sd.y, r.sd.z, r.stmax);
-            sqout[3 * (size_t)ns + 2] = make_float4(r.contrib.x, r.contrib.y, r.contrib.z,
-                                                    __uint_as_float(producer_root_word(lds_root, r.so, r.sd, r.stmax)));
+            sqout[3 * (size_t)ns + 2] = make_float4(r.contrib.x, r.contrib.y, r.contrib.z, __uint_as_float(rws));
         }
         if (r.next) {
             qout[2 * (size_t)nr] = make_float4(rayO.x, rayO.y, rayO.z, __uint_as_float(pid));
@@ -454,7 +488,7 @@ __global__ void __launch_bounds__(kBlock) wf_shade(DevScene S, const FrameParams
             qrout[nr] = rwn;
         }
     }
-    flush_producer(P, Q, n_retired, 0);
+    flush_producer<true>(P, Q, n_retired, 0, n_dark, n_unoccluded);
 }
 
 // ---- hit sort (between extend and shade) -------------------------------------------------------------
@@ -751,7 +785,8 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
     __shared__ uint32_t ts_done;
     if (threadIdx.x == 0) ts_done = 0u;
     ts_start(Q, ts);
-    const ShadeTabs halton = load_tabs(S, lds_halton, lds_mat, lds_inst, lds_light, P.U.lightCount);   // ends with a block barrier
+    // (no staged spot_cone here: the second path tipped this kernel's scalar registers into spill slots)
+    const ShadeTabs halton = load_tabs(S, lds_halton, lds_mat, lds_inst, lds_light, nullptr, P.U.lightCount);   // ends with a block barrier
     const Uniforms& U = P.U;
     const QueueShards qs = load_queue(Q.W.counts, cur, Q.seg_cap);   // front parts first: the likely-long paths
     const uint32_t n = queue_len(qs);
@@ -763,6 +798,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
     TraceCounters tc{0, 0, 0};
     bool overflow = false;
     uint32_t n_closest = 0, n_shadow = 0;
+    uint32_t n_dark = 0;   // per lane (path_step runs under divergence): shadow rays with a ±0 contribution
     f2 zero2;
     zero2.x = 0.0f;
     zero2.y = 0.0f;
@@ -866,6 +902,10 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
     auto path_step = [&](const StepAt at) {
         StepResult r;
         shade_hit(r);
+        if (r.dark) {   // counted, not traced: no query, no kShadow mode; the path goes on as after an occluded one
+            n_shadow++;
+            n_dark++;
+        }
         if (r.shadow) {
             if (at.in_regs) {
                 contrib = r.contrib;
@@ -1149,7 +1189,7 @@ wf_finish_step(DevScene S, const FrameParams* __restrict__ Pp, WfParams Q, int c
     }
 #undef RT_DX
     ts_end(Q, ts, &ts_done);
-    flush_counters(P, n_closest, n_shadow, 0, tc, COUNT, overflow);
+    flush_counters<true>(P, n_closest, n_shadow, 0, tc, COUNT, overflow, false, 0u, n_dark);
 }
 
 // ---- motion-adaptive extra samples (:779-789) -----------------------------------------------------------
