@@ -27,6 +27,8 @@
  *                              of the caller's rays against the built scene
  *   rt_resolve_hits / rt_shade_hits  what such a kernel does with the hit: the Resource-buffer
  *                              reads (:324-456) and the shading up to the next ray (:517-774)
+ *   rt_*_indirect              the same queries with their record count read from device memory
+ *                              (indirect dispatch: a compaction's count feeds the next launch)
  *   rt_read_radiance/rt_read_aux  (no reference equivalent: the reference never reads back;
  *                              replaces presenting dstTex/depthTex/motionTex to MetalFX)
  *
@@ -625,7 +627,8 @@ rt_status rt_shade_hits_on(rt_ctx* ctx, const rt_shade_opts* opts, const rt_ray*
  *                        -> rt_compact_paths(RT_PATH_ALIVE: next rays + paths) } until count == 0
  *   -> rt_average_samples
  * equals rt_render_frame's radiance of frame 0 bit for bit, all four channels.  The host's only
- * part per round is reading the 4-byte count of each compaction (the `n` of the next launches).
+ * part per round is reading the 4-byte count of each compaction (the `n` of the next launches),
+ * and with the _indirect forms (device-count queries, below) not even that.
  *
  * All data pointers are DEVICE pointers.  Every call follows rt_resolve_hits' conventions: it
  * enqueues launches only (no host wait, no allocation in the steady state); the plain form runs
@@ -711,6 +714,84 @@ rt_status rt_retire_paths_on(rt_ctx* ctx, const rt_path* paths, uint32_t n, floa
 rt_status rt_average_samples(rt_ctx* ctx, const float* samples, uint32_t pixels, uint32_t spp, float* rgba);
 rt_status rt_average_samples_on(rt_ctx* ctx, const float* samples, uint32_t pixels, uint32_t spp, float* rgba,
                                 void* hip_stream);
+
+/* ---- Device-count queries: the record count read on the device ------------------------------------
+ * The indirect-dispatch form of the seven queries whose `n` a compaction produces.  The count
+ * stays in device memory: rt_compact_paths_indirect writes it, the next queries read it, and the
+ * host never waits for it.  Each signature is the direct form's with `uint32_t n` replaced by
+ * `const rt_device_count* cnt` (rt_connect_paths_indirect: its `m`; its `n` stays a host bound).
+ * Both entry points of a query have one: X_indirect runs on the context's stream as X does,
+ * X_on_indirect on `hip_stream` as X_on does (the suffix names the form of that entry point).
+ * The struct itself is host memory, read before the call returns.  rt_camera_paths and
+ * rt_average_samples have no such form: the host knows their sizes.
+ *   rt_compact_paths_indirect(.., &in, .., &out_word) -> rt_trace_closest_indirect(.., {&out_word, max}, ..)
+ *   -> rt_resolve_hits_indirect(.., {&out_word, max}, ..) -> ...   with no host wait anywhere. */
+typedef struct rt_device_count {   /* 16 B */
+    const uint32_t* count;         /* DEVICE pointer, 4-byte aligned: the number of records, read on
+                                      the device when the launch runs */
+    uint32_t        max;           /* host bound: the arrays hold this many records */
+    uint32_t        _pad;
+} rt_device_count;
+RT_STATIC_ASSERT(sizeof(rt_device_count) == 16, "rt_device_count is 16 B");
+
+/* Semantics:
+ *  - Effective count: min(*cnt->count, cnt->max), read once per launch on the device, ordered on
+ *    the stream the query runs on: a `count` written by an earlier rt_compact_paths* on the same
+ *    stream is the one seen, with no host wait between.  The library never reads `count` on the
+ *    host.
+ *  - Records at or beyond the effective count are neither read nor written.  A *count above max
+ *    clamps to max; nothing past max is addressed.
+ *  - The host uses `max` wherever the direct form uses `n`: the pointer checks, the grid size, the
+ *    compaction's temporary storage, the early return.
+ *  - max == 0: RT_OK, nothing is launched and nothing is written (`count` may then be NULL).
+ *  - An effective count of 0 with max > 0 is a normal launch: it writes no record;
+ *    rt_compact_paths_indirect still writes *count_out = 0; a trace still counts as a query in
+ *    rt_query_stats, with rays == 0.
+ *  - rt_compact_paths_indirect chains: *count_out is always written when max > 0, so it can be the
+ *    next call's cnt->count.  count_out == cnt->count is RT_ERR_INVALID_ARG (the copy launch
+ *    reads the input count after the scan launch wrote the output).
+ *  - Statistics: for the indirect traces rt_query_stats.rays, hits, node_visits and tri_tests are
+ *    the device-counted figures of the effective count; grid_blocks is what `max` gave.
+ *  - Geometry generation, ordering against updates, query slots, rt_wait, rt_destroy, aliasing
+ *    and the guarantee that frames rendered with queries interleaved are bit-identical: exactly
+ *    as for the direct forms.  The results of the first `effective count` records are the direct
+ *    form's with n = that count, bit for bit.
+ *  - Errors: cnt == NULL, cnt->count == NULL with max > 0, or a count pointer not 4-byte aligned:
+ *    RT_ERR_INVALID_ARG before any launch; then the direct form's errors with n = max.
+ *  - Lifetime: the caller keeps `count` alive, and does not write it, until the query has
+ *    finished. */
+rt_status rt_trace_closest_indirect(rt_ctx* ctx, const rt_ray* rays, const rt_device_count* cnt, rt_ray_hit* hits);
+rt_status rt_trace_closest_on_indirect(rt_ctx* ctx, const rt_ray* rays, const rt_device_count* cnt, rt_ray_hit* hits,
+                                       void* hip_stream);
+rt_status rt_trace_any_indirect(rt_ctx* ctx, const rt_ray* rays, const rt_device_count* cnt, uint32_t* occluded);
+rt_status rt_trace_any_on_indirect(rt_ctx* ctx, const rt_ray* rays, const rt_device_count* cnt, uint32_t* occluded,
+                                   void* hip_stream);
+rt_status rt_resolve_hits_indirect(rt_ctx* ctx, const rt_ray* rays, const rt_ray_hit* hits, const rt_device_count* cnt,
+                                   rt_surface* surfaces, rt_surface_material* materials);
+rt_status rt_resolve_hits_on_indirect(rt_ctx* ctx, const rt_ray* rays, const rt_ray_hit* hits, const rt_device_count* cnt,
+                                      rt_surface* surfaces, rt_surface_material* materials, void* hip_stream);
+rt_status rt_shade_hits_indirect(rt_ctx* ctx, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                                 const rt_surface_material* materials, const float* randoms, const rt_device_count* cnt,
+                                 rt_path* paths, rt_ray* next_rays, rt_ray* shadow_rays, float* contrib);
+rt_status rt_shade_hits_on_indirect(rt_ctx* ctx, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                                    const rt_surface_material* materials, const float* randoms, const rt_device_count* cnt,
+                                    rt_path* paths, rt_ray* next_rays, rt_ray* shadow_rays, float* contrib,
+                                    void* hip_stream);
+rt_status rt_compact_paths_indirect(rt_ctx* ctx, const rt_path* paths, const rt_device_count* cnt, uint32_t mask,
+                                    const rt_compact_stream* streams, uint32_t stream_count, uint32_t* index,
+                                    uint32_t* count);
+rt_status rt_compact_paths_on_indirect(rt_ctx* ctx, const rt_path* paths, const rt_device_count* cnt, uint32_t mask,
+                                       const rt_compact_stream* streams, uint32_t stream_count, uint32_t* index,
+                                       uint32_t* count, void* hip_stream);
+rt_status rt_connect_paths_indirect(rt_ctx* ctx, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                                    const uint32_t* occluded, const rt_device_count* cnt);
+rt_status rt_connect_paths_on_indirect(rt_ctx* ctx, rt_path* paths, uint32_t n, const float* contrib,
+                                       const uint32_t* index, const uint32_t* occluded, const rt_device_count* cnt,
+                                       void* hip_stream);
+rt_status rt_retire_paths_indirect(rt_ctx* ctx, const rt_path* paths, const rt_device_count* cnt, float* samples,
+                                   uint32_t tags);
+rt_status rt_retire_paths_on_indirect(rt_ctx* ctx, const rt_path* paths, const rt_device_count* cnt, float* samples,
+                                      uint32_t tags, void* hip_stream);
 
 /* Library build identification (kernel code object arch etc). */
 const char* rt_version(void);

@@ -251,6 +251,10 @@ class CompactStream(C.Structure):  # rt_compact_stream: 24 B
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("words", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class DeviceCount(C.Structure):  # rt_device_count: 16 B
+    _fields_ = [("count", C.c_void_p), ("max", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class QueryStats(C.Structure):  # rt_query_stats
     _fields_ = [
         ("rays", C.c_uint64),
@@ -319,6 +323,10 @@ EXPORTED_SYMBOLS = [
     "rt_resolve_hits", "rt_resolve_hits_on", "rt_shade_hits", "rt_shade_hits_on",
     "rt_camera_paths", "rt_camera_paths_on", "rt_compact_paths", "rt_compact_paths_on", "rt_connect_paths",
     "rt_connect_paths_on", "rt_retire_paths", "rt_retire_paths_on", "rt_average_samples", "rt_average_samples_on",
+    "rt_trace_closest_indirect", "rt_trace_closest_on_indirect", "rt_trace_any_indirect", "rt_trace_any_on_indirect",
+    "rt_resolve_hits_indirect", "rt_resolve_hits_on_indirect", "rt_shade_hits_indirect", "rt_shade_hits_on_indirect",
+    "rt_compact_paths_indirect", "rt_compact_paths_on_indirect", "rt_connect_paths_indirect",
+    "rt_connect_paths_on_indirect", "rt_retire_paths_indirect", "rt_retire_paths_on_indirect",
     "rt_version", "rt_debug_trace_host", "rt_debug_resolve_host", "rt_debug_shade_host",
     "rt_debug_camera_paths_host", "rt_debug_compact_paths_host",
     # rt_scene.h
@@ -329,6 +337,12 @@ EXPORTED_SYMBOLS = [
     "rt_camera_default", "rt_camera_orbit", "rt_uniforms_default", "rt_random_offsets",
 ]
 
+
+# Queries whose two entry points X and X_on each have an indirect form, X_indirect and X_on_indirect:
+# the record count (rt_connect_paths: m, its last argument) is a `const rt_device_count*` in place of
+# the uint32_t.
+INDIRECT = {"rt_trace_closest": 2, "rt_trace_any": 2, "rt_resolve_hits": 3, "rt_shade_hits": 6, "rt_compact_paths": 2,
+            "rt_connect_paths": 6, "rt_retire_paths": 2}   # name: index of the count among the arguments
 
 # Entry points with an `_on` twin: the same arguments plus a trailing HIP stream handle (void*).
 ON_TWINS = ("rt_pack_tiles", "rt_unpack_tiles", "rt_trace_closest", "rt_trace_any", "rt_resolve_hits", "rt_shade_hits",
@@ -416,6 +430,11 @@ def declare(lib):
     }
     for name in ON_TWINS:
         sig[name + "_on"] = (sig[name][0], sig[name][1] + [vp])
+    for name, k in INDIRECT.items():
+        for entry in (name, name + "_on"):
+            res, args = sig[entry]
+            assert args[k] is C.c_uint32, entry
+            sig[entry + "_indirect"] = (res, args[:k] + [P(DeviceCount)] + args[k + 1:])
     for name, (res, args) in sig.items():
         if name in OPTIONAL and not hasattr(lib, name):
             continue   # measurement hook absent from an older library (A/B runs); compute entry points are required

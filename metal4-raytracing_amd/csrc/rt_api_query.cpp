@@ -8,7 +8,9 @@
 // (rt_camera_paths, rt_compact_paths, rt_connect_paths, rt_retire_paths, rt_average_samples) close
 // that loop, each one slot and one launch (the compaction: three, on the slot's own scratch).
 // Every entry point is its argument checks, then enqueue_query around the parameter fill and the
-// launch.  Queries share nothing writable with frames: their counters, events and statistics are
+// launch.  The _indirect forms are the same functions with a Count that carries a device word: the
+// host then uses its `n` as the direct forms do (checks, grid, scratch, early return) and never
+// reads the word; the kernels clamp it to `n` (launch_count, rt_kernels.h).  Queries share nothing writable with frames: their counters, events and statistics are
 // their own (QuerySlot, rt_ctx.h).
 #include <algorithm>
 #include <cstring>
@@ -120,10 +122,29 @@ rt_status enqueue_query(rt_ctx* c, QueryStream where, bool counted, Body body) {
     return commit_query(c, *q, stream, counted);
 }
 
+// A query's record count: the host's n (the direct forms), or a device word bounded by n (the
+// _indirect forms; dev is set exactly when n > 0 there).
+struct Count {
+    uint32_t n;
+    const uint32_t* dev;
+    Count(uint32_t n_, const uint32_t* dev_ = nullptr) : n(n_), dev(dev_) {}
+};
+
+// What every _indirect entry point checks before it calls its direct form's function with a Count.
+template <class Call>
+rt_status with_device_count(rt_ctx* c, const rt_device_count* cnt, Call call) {
+    if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
+    if (!cnt) FAIL(c, RT_ERR_INVALID_ARG, "null device count");
+    if (cnt->max > 0 && !cnt->count) FAIL(c, RT_ERR_INVALID_ARG, "null count pointer with max > 0");
+    if ((uintptr_t)cnt->count & 3u) FAIL(c, RT_ERR_INVALID_ARG, "the count pointer must be 4-byte aligned");
+    return call(Count(cnt->max, cnt->max > 0 ? cnt->count : nullptr));
+}
+
 // a small batch does not launch the whole chip
 unsigned query_grid(unsigned resident, uint32_t n) { return std::min(resident, (n - 1u) / (unsigned)kBlock + 1u); }
 
-rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, QueryStream where) {
+rt_status trace(rt_ctx* c, const rt_ray* rays, Count cnt, void* out, bool any, QueryStream where) {
+    const uint32_t n = cnt.n;
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (n > 0) {
         if (!rays || !out) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
@@ -147,6 +168,7 @@ rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, 
         Q.occluded = any ? (uint32_t*)out : nullptr;
         Q.sub_first = (const uint32_t*)c->d_sub_first.p;
         Q.state = (unsigned long long*)q.state.p;
+        Q.count = cnt.dev;
         Q.n = n;
         Q.refill_min = c->tuning.refill_min;
         q.any = any;
@@ -162,8 +184,9 @@ rt_status trace(rt_ctx* c, const rt_ray* rays, uint32_t n, void* out, bool any, 
     });
 }
 
-rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_t n, rt_surface* surfaces,
+rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, Count cnt, rt_surface* surfaces,
                   rt_surface_material* materials, QueryStream where) {
+    const uint32_t n = cnt.n;
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (n > 0) {
         if (!rays || !hits || !surfaces) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
@@ -195,6 +218,7 @@ rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_
         P.hits = (const float4*)hits;
         P.surfaces = (float4*)surfaces;
         P.materials = (float4*)materials;
+        P.count = cnt.dev;
         P.n = n;
         launch_resolve(S, P, query_grid(resolve_resident_blocks(), n), stream);
         return RT_OK;
@@ -203,8 +227,9 @@ rt_status resolve(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, uint32_
 
 // From here on no query reads the geometry: shading reads the lights and the Halton table only.
 rt_status shade(rt_ctx* c, const rt_shade_opts* o, const rt_ray* rays, const rt_surface* surfaces,
-                const rt_surface_material* materials, const float* randoms, uint32_t n, rt_path* paths, rt_ray* next_rays,
+                const rt_surface_material* materials, const float* randoms, Count cnt, rt_path* paths, rt_ray* next_rays,
                 rt_ray* shadow_rays, float* contrib, QueryStream where) {
+    const uint32_t n = cnt.n;
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (rt_status st = validate_shade(c, o, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib))
         return st;
@@ -224,6 +249,7 @@ rt_status shade(rt_ctx* c, const rt_shade_opts* o, const rt_ray* rays, const rt_
         P.contrib = (float4*)contrib;
         P.lights = (const Light*)c->d_lights.p;
         P.halton = (const HaltonDim*)c->d_halton.p;
+        P.count = cnt.dev;
         P.n = n;
         P.shading_mode = o->shading_mode;
         P.max_bounces = o->max_bounces;
@@ -261,10 +287,13 @@ rt_status camera_paths(rt_ctx* c, const Uniforms* u, const rt_camera_opts* o, co
     });
 }
 
-rt_status compact_paths(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
+rt_status compact_paths(rt_ctx* c, const rt_path* paths, Count cnt, uint32_t mask, const rt_compact_stream* streams,
                         uint32_t stream_count, uint32_t* index, uint32_t* count, QueryStream where) {
+    const uint32_t n = cnt.n;
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (rt_status st = validate_compact(c, paths, n, mask, streams, stream_count, index, count)) return st;
+    // the copy launch reads the input count after the scan launch wrote the output
+    if (cnt.dev && cnt.dev == count) FAIL(c, RT_ERR_INVALID_ARG, "count is the device count it is compacted by");
     if (n == 0) return RT_OK;
     return enqueue_query(c, where, false, [&](QuerySlot& q, const Geo&, hipStream_t stream) -> rt_status {
         // The slot's own storage: its previous query has been harvested, so nothing reads what a growth
@@ -286,6 +315,7 @@ rt_status compact_paths(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t ma
         P.tiles = compact_tiles(n);
         P.bits = (unsigned long long*)q.scratch.p;
         P.tile_count = (uint32_t*)(P.bits + (size_t)P.tiles * kCompactSegs);
+        P.n_count = cnt.dev;
         P.n = n;
         P.mask = mask;
         P.streams = stream_count;
@@ -295,7 +325,8 @@ rt_status compact_paths(rt_ctx* c, const rt_path* paths, uint32_t n, uint32_t ma
 }
 
 rt_status connect_paths(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
-                        const uint32_t* occluded, uint32_t m, QueryStream where) {
+                        const uint32_t* occluded, Count cnt, QueryStream where) {
+    const uint32_t m = cnt.n;
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (m > 0 && n > 0) {
         if (!paths || !contrib || !occluded) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
@@ -304,13 +335,14 @@ rt_status connect_paths(rt_ctx* c, rt_path* paths, uint32_t n, const float* cont
     }
     if (m == 0 || n == 0) return RT_OK;
     return enqueue_query(c, where, false, [&](QuerySlot&, const Geo&, hipStream_t stream) -> rt_status {
-        const ConnectParams P{(float4*)paths, (const float4*)contrib, index, occluded, n, m};
+        const ConnectParams P{(float4*)paths, (const float4*)contrib, index, occluded, cnt.dev, n, m};
         launch_connect(P, query_grid(path_resident_blocks(), m), stream);
         return RT_OK;
     });
 }
 
-rt_status retire_paths(rt_ctx* c, const rt_path* paths, uint32_t n, float* samples, uint32_t tags, QueryStream where) {
+rt_status retire_paths(rt_ctx* c, const rt_path* paths, Count cnt, float* samples, uint32_t tags, QueryStream where) {
+    const uint32_t n = cnt.n;
     if (!c) FAIL(c, RT_ERR_INVALID_ARG, "null ctx");
     if (n > 0 && tags > 0) {
         if (!paths || !samples) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
@@ -318,7 +350,7 @@ rt_status retire_paths(rt_ctx* c, const rt_path* paths, uint32_t n, float* sampl
     }
     if (n == 0 || tags == 0) return RT_OK;
     return enqueue_query(c, where, false, [&](QuerySlot&, const Geo&, hipStream_t stream) -> rt_status {
-        const RetireParams P{(const float4*)paths, (float4*)samples, n, tags};
+        const RetireParams P{(const float4*)paths, (float4*)samples, cnt.dev, n, tags};
         launch_retire(P, query_grid(path_resident_blocks(), n), stream);
         return RT_OK;
     });
@@ -433,6 +465,93 @@ rt_status rt_average_samples(rt_ctx* c, const float* samples, uint32_t pixels, u
 
 rt_status rt_average_samples_on(rt_ctx* c, const float* samples, uint32_t pixels, uint32_t spp, float* rgba, void* stream) {
     return average_samples(c, samples, pixels, spp, rgba, QueryStream::on(stream));
+}
+
+// The _indirect forms: the direct form's function with the device count checked and handed on.
+rt_status rt_trace_closest_indirect(rt_ctx* c, const rt_ray* rays, const rt_device_count* cnt, rt_ray_hit* hits) {
+    return with_device_count(c, cnt, [&](Count n) { return trace(c, rays, n, hits, false, QueryStream::of_ctx()); });
+}
+
+rt_status rt_trace_closest_on_indirect(rt_ctx* c, const rt_ray* rays, const rt_device_count* cnt, rt_ray_hit* hits,
+                                       void* stream) {
+    return with_device_count(c, cnt, [&](Count n) { return trace(c, rays, n, hits, false, QueryStream::on(stream)); });
+}
+
+rt_status rt_trace_any_indirect(rt_ctx* c, const rt_ray* rays, const rt_device_count* cnt, uint32_t* occluded) {
+    return with_device_count(c, cnt, [&](Count n) { return trace(c, rays, n, occluded, true, QueryStream::of_ctx()); });
+}
+
+rt_status rt_trace_any_on_indirect(rt_ctx* c, const rt_ray* rays, const rt_device_count* cnt, uint32_t* occluded,
+                                   void* stream) {
+    return with_device_count(c, cnt, [&](Count n) { return trace(c, rays, n, occluded, true, QueryStream::on(stream)); });
+}
+
+rt_status rt_resolve_hits_indirect(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, const rt_device_count* cnt,
+                                   rt_surface* surfaces, rt_surface_material* materials) {
+    return with_device_count(
+        c, cnt, [&](Count n) { return resolve(c, rays, hits, n, surfaces, materials, QueryStream::of_ctx()); });
+}
+
+rt_status rt_resolve_hits_on_indirect(rt_ctx* c, const rt_ray* rays, const rt_ray_hit* hits, const rt_device_count* cnt,
+                                      rt_surface* surfaces, rt_surface_material* materials, void* stream) {
+    return with_device_count(
+        c, cnt, [&](Count n) { return resolve(c, rays, hits, n, surfaces, materials, QueryStream::on(stream)); });
+}
+
+rt_status rt_shade_hits_indirect(rt_ctx* c, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                                 const rt_surface_material* materials, const float* randoms, const rt_device_count* cnt,
+                                 rt_path* paths, rt_ray* next_rays, rt_ray* shadow_rays, float* contrib) {
+    return with_device_count(c, cnt, [&](Count n) {
+        return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib,
+                     QueryStream::of_ctx());
+    });
+}
+
+rt_status rt_shade_hits_on_indirect(rt_ctx* c, const rt_shade_opts* opts, const rt_ray* rays, const rt_surface* surfaces,
+                                    const rt_surface_material* materials, const float* randoms, const rt_device_count* cnt,
+                                    rt_path* paths, rt_ray* next_rays, rt_ray* shadow_rays, float* contrib, void* stream) {
+    return with_device_count(c, cnt, [&](Count n) {
+        return shade(c, opts, rays, surfaces, materials, randoms, n, paths, next_rays, shadow_rays, contrib,
+                     QueryStream::on(stream));
+    });
+}
+
+rt_status rt_compact_paths_indirect(rt_ctx* c, const rt_path* paths, const rt_device_count* cnt, uint32_t mask,
+                                    const rt_compact_stream* streams, uint32_t stream_count, uint32_t* index,
+                                    uint32_t* count) {
+    return with_device_count(c, cnt, [&](Count n) {
+        return compact_paths(c, paths, n, mask, streams, stream_count, index, count, QueryStream::of_ctx());
+    });
+}
+
+rt_status rt_compact_paths_on_indirect(rt_ctx* c, const rt_path* paths, const rt_device_count* cnt, uint32_t mask,
+                                       const rt_compact_stream* streams, uint32_t stream_count, uint32_t* index,
+                                       uint32_t* count, void* stream) {
+    return with_device_count(c, cnt, [&](Count n) {
+        return compact_paths(c, paths, n, mask, streams, stream_count, index, count, QueryStream::on(stream));
+    });
+}
+
+rt_status rt_connect_paths_indirect(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                                    const uint32_t* occluded, const rt_device_count* cnt) {
+    return with_device_count(
+        c, cnt, [&](Count m) { return connect_paths(c, paths, n, contrib, index, occluded, m, QueryStream::of_ctx()); });
+}
+
+rt_status rt_connect_paths_on_indirect(rt_ctx* c, rt_path* paths, uint32_t n, const float* contrib, const uint32_t* index,
+                                       const uint32_t* occluded, const rt_device_count* cnt, void* stream) {
+    return with_device_count(
+        c, cnt, [&](Count m) { return connect_paths(c, paths, n, contrib, index, occluded, m, QueryStream::on(stream)); });
+}
+
+rt_status rt_retire_paths_indirect(rt_ctx* c, const rt_path* paths, const rt_device_count* cnt, float* samples,
+                                   uint32_t tags) {
+    return with_device_count(c, cnt, [&](Count n) { return retire_paths(c, paths, n, samples, tags, QueryStream::of_ctx()); });
+}
+
+rt_status rt_retire_paths_on_indirect(rt_ctx* c, const rt_path* paths, const rt_device_count* cnt, float* samples,
+                                      uint32_t tags, void* stream) {
+    return with_device_count(c, cnt, [&](Count n) { return retire_paths(c, paths, n, samples, tags, QueryStream::on(stream)); });
 }
 
 rt_status rt_get_query_stats(rt_ctx* c, rt_query_stats* out) {

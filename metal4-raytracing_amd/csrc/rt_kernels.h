@@ -141,12 +141,25 @@ bool lbvh_build(const LbvhInput& in, const LbvhOutput& out, void* scratch, hipSt
 constexpr int kRqChunk = 64;          // rays per chunk grab
 constexpr int kRqChunkCounters = 8;   // one per XCD (blockIdx % 8)
 constexpr size_t kRqStateBytes = sizeof(unsigned long long) * kCounterWords + 128 * kRqChunkCounters;
+
+// The record count of a query launch.  Every rq_* parameter block carries the host's count and a
+// device word `count` that is null for the direct forms.  With a word (the _indirect forms of
+// include/rt_api.h) the host's count is only a bound: the launch runs over min(*count, bound),
+// read once at kernel entry and kept in a scalar register, so every loop bound stays wave-uniform.
+// The word was written by an earlier launch on the stream (the kernel boundary orders it).
+__device__ __forceinline__ uint32_t launch_count(const uint32_t* count, uint32_t bound) {
+    if (!count) return bound;
+    const uint32_t v = *count;
+    return __builtin_amdgcn_readfirstlane(v < bound ? v : bound);
+}
+
 struct RqParams {
     const float4* rays;
     float4* hits;               // closest hit: two 16-B words per ray (rt_ray_hit)
     uint32_t* occluded;         // any hit: one word per ray
     const uint32_t* sub_first;  // first scene-wide triangle id of submesh [mesh * max_submeshes + submesh]
     unsigned long long* state;
+    const uint32_t* count;      // or null (launch_count)
     uint32_t n;
     int refill_min;
 };
@@ -163,6 +176,7 @@ struct RsParams {
     const float4* hits;     // two words per record (rt_ray_hit)
     float4* surfaces;
     float4* materials;      // or null
+    const uint32_t* count;  // or null (launch_count)
     uint32_t n;
 };
 unsigned resolve_resident_blocks();
@@ -183,6 +197,7 @@ struct ShParams {
     float4* contrib;           // one
     const Light* lights;
     const HaltonDim* halton;
+    const uint32_t* count;     // or null (launch_count)
     uint32_t n;
     int shading_mode, max_bounces, light_count;
 };
@@ -206,11 +221,13 @@ struct ConnectParams {
     const float4* contrib;
     const uint32_t* index;     // or null: j itself
     const uint32_t* occluded;
+    const uint32_t* count;     // or null (launch_count): bounds m, never n
     uint32_t n, m;
 };
 struct RetireParams {
     const float4* paths;
     float4* samples;
+    const uint32_t* count;     // or null (launch_count)
     uint32_t n, tags;
 };
 struct AverageParams {
@@ -227,7 +244,8 @@ struct CompactParams {
     uint32_t* count;
     unsigned long long* bits;       // kCompactSegs selection words per tile
     uint32_t* tile_count;           // per tile: selected count, after the scan its offset
-    uint32_t n, mask, streams, tiles;
+    const uint32_t* n_count;        // or null (launch_count): the input count; never equal to `count`
+    uint32_t n, mask, streams, tiles;   // tiles = compact_tiles(n): what bits / tile_count are sized and laid out for
 };
 unsigned path_resident_blocks();
 void launch_camera(const CamParams& P, unsigned blocks, hipStream_t stream);

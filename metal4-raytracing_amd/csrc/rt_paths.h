@@ -74,7 +74,7 @@ RT_HD float4 average_pixel(const float4* s, uint32_t spp) {
 constexpr uint32_t kCompactTile = 1024;
 constexpr uint32_t kCompactSegs = kCompactTile / 64;
 constexpr uint32_t kCompactMaxStreams = 4;
-RT_HD uint32_t compact_tiles(uint32_t n) { return (n - 1u) / kCompactTile + 1u; }   // n > 0
+RT_HD uint32_t compact_tiles(uint32_t n) { return (n - 1u) / kCompactTile + 1u; }   // n > 0 (a device count of 0: launch_tiles, rt_query.hip)
 RT_HD size_t compact_scratch_bytes(uint32_t n) {
     return (size_t)compact_tiles(n) * (kCompactSegs * sizeof(unsigned long long) + sizeof(uint32_t));
 }

@@ -4,7 +4,9 @@
 // `intersector.intersect` called from a kernel other than raytracingKernel.  Next to it the two
 // per-record kernels of a user-side integrator: rq_resolve (rt_resolve_hits) and rq_shade
 // (rt_shade_hits), and the path queries that close its loop: rq_camera, rq_connect, rq_retire,
-// rq_average and the three launches of rt_compact_paths.
+// rq_average and the three launches of rt_compact_paths.  Every kernel whose record count a
+// compaction can produce reads it through launch_count (rt_kernels.h): the host's n, or for the
+// _indirect entry points a device word clamped to it, so the grid needs a bound only.
 #include <hip/hip_runtime.h>
 
 #include "rt_kernels.h"
@@ -37,7 +39,8 @@ rq_trace(DevScene S, RqParams Q) {
     int* stack = &lds_stack[threadIdx.x];
 
     uint32_t* const chunk_ctr = reinterpret_cast<uint32_t*>(Q.state + kCounterWords);
-    const uint32_t nchunks = (Q.n - 1u) / (uint32_t)kRqChunk + 1u;   // n > 0
+    const uint32_t n = launch_count(Q.count, Q.n);
+    const uint32_t nchunks = (n - 1u) / (uint32_t)kRqChunk + 1u;   // n > 0: read inside the loop only
     const uint32_t xcd = blockIdx.x & (uint32_t)(kRqChunkCounters - 1);
     uint32_t tries = 0;   // counters found exhausted so far (wave-uniform)
     uint32_t wnext = 0, wend = 0;
@@ -50,7 +53,9 @@ rq_trace(DevScene S, RqParams Q) {
     Trav T;
     trav_start(T, mk3(0, 0, 0), mk3(1, 0, 0), 0.0f);
 
-    while (true) {
+    // A device count of 0 (the host never launches n == 0): no wave enters, no chunk counter is
+    // touched, and every wave flushes its zeros below.
+    if (n != 0u) while (true) {
         // refill idle lanes from the wave's chunk
         const unsigned long long idle = __ballot(!active);
         const bool refill = __popcll(idle) >= Q.refill_min || idle == ~0ull;
@@ -61,12 +66,14 @@ rq_trace(DevScene S, RqParams Q) {
                 if (lane_id() == 0) k = atomicAdd(&chunk_ctr[part * kChunkCtrStride], 1u);
                 k = __builtin_amdgcn_readfirstlane(k);
                 // chunk k of counter `part`: k stays below nchunks / 8 + the waves of the grid, far from 2^29
+                // (a wave adds to a counter it found exhausted once, then moves on: the second term is the
+                // grid's, at most the resident waves, however far a device count falls below its bound)
                 const uint32_t c = k * (uint32_t)kRqChunkCounters + part;
                 if (c >= nchunks) {
                     ++tries;
                 } else {
                     wnext = c * (uint32_t)kRqChunk;   // < n
-                    wend = Q.n - wnext < (uint32_t)kRqChunk ? Q.n : wnext + (uint32_t)kRqChunk;
+                    wend = n - wnext < (uint32_t)kRqChunk ? n : wnext + (uint32_t)kRqChunk;
                 }
             }
         }
@@ -121,7 +128,8 @@ rq_trace(DevScene S, RqParams Q) {
 template <bool MATERIAL, bool TEXTURED>
 __global__ void __launch_bounds__(kBlock) rq_resolve(DevScene S, RsParams P) {
     const size_t stride = (size_t)gridDim.x * kBlock;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)P.n; i += stride) {
+    const size_t n = launch_count(P.count, P.n);
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const float4 o4 = P.rays[2 * i], d4 = P.rays[2 * i + 1];
         const float4 h0 = P.hits[2 * i];
         const uint4 h1 = reinterpret_cast<const uint4*>(P.hits)[2 * i + 1];
@@ -154,7 +162,8 @@ template <bool RANDOMS>
 __global__ void __launch_bounds__(kBlock) rq_shade(ShParams P) {
     const ScatterOpts U{P.shading_mode, P.max_bounces, P.light_count};
     const size_t stride = (size_t)gridDim.x * kBlock;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)P.n; i += stride) {
+    const size_t n = launch_count(P.count, P.n);
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const float4 d4 = P.rays[2 * i + 1];
         const float4* const sp = P.surfaces + 4 * i;
         const float4 s0 = sp[0], s1 = sp[1], s2 = sp[2];
@@ -204,10 +213,12 @@ __global__ void __launch_bounds__(kBlock) rq_camera(CamParams P) {
 }
 
 // Shadow ray j (of m) belongs to record index[j] (or j); an unoccluded one adds its record's
-// contribution.  Records at or above n are skipped before anything of theirs is addressed.
+// contribution.  Records at or above n are skipped before anything of theirs is addressed.  A
+// device count bounds the shadow rays (m); n is always the host's.
 __global__ void __launch_bounds__(kBlock) rq_connect(ConnectParams P) {
     const size_t stride = (size_t)gridDim.x * kBlock;
-    for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < (size_t)P.m; j += stride) {
+    const size_t m = launch_count(P.count, P.m);
+    for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < m; j += stride) {
         if (P.occluded[j] != 0u) continue;
         const size_t i = P.index ? (size_t)P.index[j] : j;
         if (i >= (size_t)P.n) continue;
@@ -217,7 +228,8 @@ __global__ void __launch_bounds__(kBlock) rq_connect(ConnectParams P) {
 
 __global__ void __launch_bounds__(kBlock) rq_retire(RetireParams P) {
     const size_t stride = (size_t)gridDim.x * kBlock;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)P.n; i += stride) {
+    const size_t n = launch_count(P.count, P.n);
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const float4 p1 = P.paths[3 * i + 1];
         const uint32_t tag = reinterpret_cast<const uint4*>(P.paths)[3 * i + 2].w;
         if ((f2u(p1.w) & RT_PATH_ALIVE) == 0u && tag < P.tags) P.samples[tag] = retire_word(p1);
@@ -243,18 +255,23 @@ __global__ void __launch_bounds__(kBlock) rq_average(AverageParams P) {
 //     selected source indices are staged in LDS in rank order, and consecutive threads then copy
 //     consecutive 16-B words of the tile's contiguous destination range [offset, offset + cnt):
 //     coalesced stores, gathering loads.  It reads the 8-byte words of launch 1, not the flags.
+// With a device count each launch runs over the tiles of min(*n_count, n) only (none for 0: the
+// scan still writes *count = 0); the scratch keeps the layout of P.tiles = compact_tiles(n).
 static_assert(kCompactTile % kBlock == 0 && kBlock % 64 == 0 && kCompactSegs <= kBlock, "tile geometry");
+
+__device__ __forceinline__ uint32_t launch_tiles(uint32_t n) { return n ? compact_tiles(n) : 0u; }   // <= P.tiles
 
 __global__ void __launch_bounds__(kBlock) rq_compact_count(CompactParams P) {
     __shared__ uint32_t seg_cnt[kCompactSegs];
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t* const flags = reinterpret_cast<const uint32_t*>(P.paths) + 7;   // rt_path.flags, 12 words apart
-    for (uint32_t tile = blockIdx.x; tile < P.tiles; tile += gridDim.x) {
+    const uint32_t n = launch_count(P.n_count, P.n), tiles = launch_tiles(n);
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const size_t first = (size_t)tile * kCompactTile;
         #pragma unroll
         for (uint32_t k = 0; k < kCompactTile / kBlock; ++k) {
             const size_t i = first + k * kBlock + threadIdx.x;
-            const bool sel = i < (size_t)P.n && (flags[12 * i] & P.mask) != 0u;
+            const bool sel = i < (size_t)n && (flags[12 * i] & P.mask) != 0u;
             const unsigned long long b = __ballot(sel);
             if (lane_id() == 0) {
                 const uint32_t seg = k * (kBlock / 64) + wave;
@@ -278,9 +295,10 @@ __global__ void __launch_bounds__(kBlock) rq_compact_scan(CompactParams P) {
     __shared__ uint32_t wave_tot[kBlock / 64];
     const uint32_t wave = threadIdx.x >> 6;
     uint32_t carry = 0;
-    for (uint32_t base = 0; base < P.tiles; base += kBlock) {
+    const uint32_t tiles = launch_tiles(launch_count(P.n_count, P.n));
+    for (uint32_t base = 0; base < tiles; base += kBlock) {
         const uint32_t t = base + threadIdx.x;
-        const uint32_t v = t < P.tiles ? P.tile_count[t] : 0u;
+        const uint32_t v = t < tiles ? P.tile_count[t] : 0u;
         const uint32_t incl = wave_incl_scan(v);
         if (lane_id() == 63) wave_tot[wave] = incl;
         __syncthreads();
@@ -290,7 +308,7 @@ __global__ void __launch_bounds__(kBlock) rq_compact_scan(CompactParams P) {
             before += w < wave ? wave_tot[w] : 0u;
             total += wave_tot[w];
         }
-        if (t < P.tiles) P.tile_count[t] = carry + before + (incl - v);
+        if (t < tiles) P.tile_count[t] = carry + before + (incl - v);
         carry += total;
         __syncthreads();   // wave_tot is rewritten by the next round
     }
@@ -313,7 +331,8 @@ __global__ void __launch_bounds__(kBlock) rq_compact_copy(CompactParams P) {
     __shared__ uint32_t seg_base[kCompactSegs + 1];
     __shared__ uint32_t sel_idx[kCompactTile];   // the tile's selected records (index within the tile) by rank
     const uint32_t wave = threadIdx.x >> 6;
-    for (uint32_t tile = blockIdx.x; tile < P.tiles; tile += gridDim.x) {
+    const uint32_t tiles = launch_tiles(launch_count(P.n_count, P.n));   // read after the scan wrote *count: the two differ
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const size_t first = (size_t)tile * kCompactTile;
         if (threadIdx.x < kCompactSegs) {
             const unsigned long long b = P.bits[(size_t)tile * kCompactSegs + threadIdx.x];

@@ -3,7 +3,9 @@
 Every query (rt_trace_closest / rt_trace_any, rt_resolve_hits, rt_shade_hits, rt_camera_paths,
 rt_compact_paths, rt_connect_paths, rt_retire_paths, rt_average_samples) goes through the same
 few helpers of RendererQueries: one device record check, one host staging, one `out=` check, one
-enqueue.  The package re-exports every public name of this module.
+enqueue.  The six whose record count a compaction produces take `count=`: the count stays on the
+device and the call goes to the entry point's _indirect form (rt_device_count).  The package
+re-exports every public name of this module.
 """
 import ctypes as C
 
@@ -294,13 +296,29 @@ class RendererQueries:
         torch.cuda.current_stream(dev).synchronize()
         return staged
 
-    def _enqueue(self, name, stream, *args):
+    def _enqueue(self, name, stream, *args, form=""):
         """Calls the entry point `name` on the renderer's stream (stream None) or its `_on` twin
-        on `stream`, with the context first; raises RTError on a status."""
+        on `stream`, with the context first; form "_indirect": that entry point's indirect form
+        (_n).  Raises RTError on a status."""
         if stream is None:
-            _check(getattr(_lib(), name)(self._ctx, *args), self._ctx)
+            _check(getattr(_lib(), name + form)(self._ctx, *args), self._ctx)
         else:
-            _check(getattr(_lib(), name + "_on")(self._ctx, *args, C.c_void_p(stream)), self._ctx)
+            _check(getattr(_lib(), name + "_on" + form)(self._ctx, *args, C.c_void_p(stream)), self._ctx)
+
+    def _n(self, count, n):
+        """The record count of a query as (entry-point suffix, argument): ("", n) for the direct
+        form, or with `count` (a 1-element int32 / uint32 tensor on the renderer's device, or a
+        Compacted: its .count) ("_indirect", rt_device_count{count, max = n} by reference)."""
+        if count is None:
+            return "", n
+        import torch
+        t = count.count if isinstance(count, Compacted) else count
+        if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                and t.numel() == 1 and t.device == self._device()):
+            raise ValueError(f"count must be a 1-element int32 / uint32 tensor on {self._device()}, or a Compacted")
+        dc = _abi.DeviceCount()
+        dc.count, dc.max = t.data_ptr(), n
+        return "_indirect", C.byref(dc)
 
     def _torch_stream(self, stream):
         """The torch stream of a HIP stream handle (0 = torch's default stream)."""
@@ -333,7 +351,7 @@ class RendererQueries:
         r[:, 7] = np.inf if tmax is None else np.asarray(tmax, np.float32)
         return r
 
-    def trace(self, rays, any_hit=False, out=None, stream=None):
+    def trace(self, rays, any_hit=False, out=None, stream=None, count=None):
         """rt_trace_closest / rt_trace_any: traces (n, 8) rays (make_rays) against the geometry the
         next draw() would see.
 
@@ -343,23 +361,33 @@ class RendererQueries:
         (views of one (n, 8) tensor), or one int32 tensor of 1 / 0 for any_hit.
 
         Host path: `rays` is a host array (anything that reshapes to (-1, 8)); it is staged through
-        torch, the query is waited for and the result comes back as numpy."""
+        torch, the query is waited for and the result comes back as numpy.
+
+        count (here and in resolve, shade, compact, connect and retire; device path only): the
+        number of records comes from device memory, a 1-element int32 / uint32 tensor or a
+        Compacted (its .count), read when the launch runs: the _indirect entry points.  Only the
+        first min(count, n) records are read and written, n being the length of the arrays given;
+        outputs come back at full length, the rest of them untouched.  No host wait: the count of
+        a compact() on the same stream feeds the next query directly."""
         import torch
         host = not isinstance(rays, torch.Tensor)
+        if host and count is not None:
+            raise ValueError("count= needs the device path")
         if host:
             r, = self._stage([("rays", np.asarray(rays, np.float32).reshape(-1, 8), 8)])
         else:
             r = self._records(rays, "rays", 8)
         n = r.shape[0]
         out = self._out(out, "out", n, None if any_hit else 8)
-        self._enqueue("rt_trace_any" if any_hit else "rt_trace_closest", stream, _ptr(r), n, _ptr(out))
+        ind, n_arg = self._n(count, n)
+        self._enqueue("rt_trace_any" if any_hit else "rt_trace_closest", stream, _ptr(r), n_arg, _ptr(out), form=ind)
         if host:
             self.wait()
             res = out.cpu().numpy()
             return res if any_hit else Hits(res, res.view(np.int32))
         return out if any_hit else Hits(out, out.view(torch.int32))
 
-    def resolve(self, rays, hits, material=True, out=None, stream=None):
+    def resolve(self, rays, hits, material=True, out=None, stream=None, count=None):
         """rt_resolve_hits: turns (n, 8) rays and their closest-hit records (a Hits object or its
         (n, 8) buffer) into surface and material records: what the renderer itself would shade at
         each hit, bit for bit, against the geometry the next draw() would see.
@@ -367,10 +395,12 @@ class RendererQueries:
         Device path (`rays` is a torch tensor; so is the hit buffer): enqueued on `stream` without
         a host wait.  `out` is an (n, 16) float32 tensor, or a pair of it and an (n, 12) one; with
         material=False no material record is written.  Host path (`rays` is a host array): staged
-        through torch, waited for, returned as numpy.  Returns a Surface."""
+        through torch, waited for, returned as numpy.  count: as in trace.  Returns a Surface."""
         import torch
         hb = hits.buffer if isinstance(hits, Hits) else hits
         host = not isinstance(rays, torch.Tensor)
+        if host and count is not None:
+            raise ValueError("count= needs the device path")
         if host:
             r, h = self._stage([("rays", np.asarray(rays, np.float32).reshape(-1, 8), 8), ("hits", hb, 8)])
         else:
@@ -382,7 +412,8 @@ class RendererQueries:
             raise ValueError("a materials tensor was given with material=False")
         surf = self._out(surf, "out surfaces", n, 16)
         mat = self._out(mat, "out materials", n, 12) if material else None
-        self._enqueue("rt_resolve_hits", stream, _ptr(r), _ptr(h), n, _ptr(surf), _ptr(mat))
+        ind, n_arg = self._n(count, n)
+        self._enqueue("rt_resolve_hits", stream, _ptr(r), _ptr(h), n_arg, _ptr(surf), _ptr(mat), form=ind)
         if host:
             self.wait()
             s, m = surf.cpu().numpy(), mat.cpu().numpy() if material else None
@@ -416,7 +447,7 @@ class RendererQueries:
         return Paths(p, p.view(np.int32))
 
     def shade(self, rays, surface, paths, randoms=None, shading_mode=None, max_bounces=None, light_count=None, out=None,
-              stream=None):
+              stream=None, count=None):
         """rt_shade_hits: what the renderer does between a resolved hit and the next ray.  `rays`
         are the (n, 8) rays that were traced, `surface` their Surface from resolve (with
         materials), `paths` a Paths (make_paths) or its (n, 12) buffer.  Returns a Shaded: the
@@ -430,9 +461,11 @@ class RendererQueries:
         enqueued on `stream` without a host wait; `out` is a triple of float32 tensors (next_rays
         (n, 8), shadow_rays (n, 8), contrib (n, 4)); next_rays may be `rays`.
         Host path (`rays` is a host array): staged through torch, waited for, returned as numpy;
-        the given paths are not modified."""
+        the given paths are not modified.  count: as in trace."""
         import torch
         host = not isinstance(rays, torch.Tensor)
+        if host and count is not None:
+            raise ValueError("count= needs the device path")
         pb = paths.buffer if isinstance(paths, Paths) else paths
         if surface.material_buffer is None:
             raise ValueError("shade needs the material records (resolve with material=True)")
@@ -455,8 +488,9 @@ class RendererQueries:
         o = _shade_opts(self.shadingMode if shading_mode is None else shading_mode,
                         self.maxBounces if max_bounces is None else max_bounces,
                         self.light_count if light_count is None else light_count)
-        self._enqueue("rt_shade_hits", stream, C.byref(o), _ptr(r), _ptr(s), _ptr(m), _ptr(rnd), n, _ptr(p),
-                      _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]))
+        ind, n_arg = self._n(count, n)
+        self._enqueue("rt_shade_hits", stream, C.byref(o), _ptr(r), _ptr(s), _ptr(m), _ptr(rnd), n_arg, _ptr(p),
+                      _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), form=ind)
         if host:
             self.wait()
             pn = p.cpu().numpy()
@@ -493,7 +527,7 @@ class RendererQueries:
         self._enqueue("rt_camera_paths", stream, C.byref(u), C.byref(o), _ptr(rnd), n, _ptr(rays), _ptr(pb))
         return rays, Paths(pb, pb.view(torch.int32))
 
-    def compact(self, paths, mask, streams=(), index=True, out=None, stream=None):
+    def compact(self, paths, mask, streams=(), index=True, out=None, stream=None, count=None):
         """rt_compact_paths: stable compaction of up to four record streams by the paths' flags:
         the records i with paths.flags[i] & mask != 0, in ascending i, what x[(flags & mask) != 0]
         gives.  `paths` is a Paths or its (n, 12) buffer; `streams` are (n, 4 * words) tensors of
@@ -502,9 +536,12 @@ class RendererQueries:
         out: a Compacted of an earlier call of the same shapes, or a tuple (outs, index, count) of
         tensors to write to (outs: one per stream, same shape and type; index / count may be None).
         Not in place: no output may be an input.  Enqueued on `stream` without a host wait;
-        Compacted.n() reads the count back."""
+        Compacted.n() reads the count back.  count: as in trace, the records compacted are the
+        first min(count, n); the count written is always a word of its own (RTError otherwise),
+        and it is written whenever n > 0, so it can be the next query's count."""
         import torch
         four = (torch.float32, torch.int32)
+        count_in = count
         pb = self._records(paths.buffer if isinstance(paths, Paths) else paths, "paths", 12)
         n = pb.shape[0]
         srcs = [self._records(x, f"stream {k}", (4, 8, 12, 16), n, four) for k, x in enumerate(streams)]
@@ -535,7 +572,9 @@ class RendererQueries:
             with torch.cuda.stream(self._torch_stream(stream) if stream is not None
                                    else torch.cuda.current_stream(self._device())):
                 count.zero_()
-        self._enqueue("rt_compact_paths", stream, _ptr(pb), n, int(mask), arr, len(srcs), _ptr(idx), _ptr(count))
+        ind, n_arg = self._n(count_in, n)
+        self._enqueue("rt_compact_paths", stream, _ptr(pb), n_arg, int(mask), arr, len(srcs), _ptr(idx), _ptr(count),
+                      form=ind)
 
         def sync(cp, stream=stream):
             if stream is None:
@@ -550,12 +589,13 @@ class RendererQueries:
 
         return Compacted(count, idx, outs, host, sync)
 
-    def connect(self, paths, contrib, occluded, index=None, m=None, stream=None):
+    def connect(self, paths, contrib, occluded, index=None, m=None, stream=None, count=None):
         """rt_connect_paths: paths.radiance[i] += contrib[i] for the first m shadow rays j that
         are not occluded (occluded[j] == 0), i = index[j] (or j without an index).  `paths`
         (Paths or buffer) is updated IN PLACE; contrib is (n, 4) float32, occluded and index int32
         vectors of at least m entries (m defaults to len(occluded)).  The index entries must be
-        distinct, as compact() makes them.  Enqueued on `stream` without a host wait."""
+        distinct, as compact() makes them.  Enqueued on `stream` without a host wait.  count: as in
+        trace, the number of shadow rays (m, then their bound) from device memory."""
         pb = self._records(paths.buffer if isinstance(paths, Paths) else paths, "paths", 12)
         n = pb.shape[0]
         con = self._records(contrib, "contrib", 4, n)
@@ -564,15 +604,17 @@ class RendererQueries:
         m = occ.shape[0] if m is None else int(m)
         if m < 0 or m > occ.shape[0] or (idx is not None and m > idx.shape[0]):
             raise ValueError(f"m = {m} is more than occluded / index hold")
-        self._enqueue("rt_connect_paths", stream, _ptr(pb), n, _ptr(con), _ptr(idx), _ptr(occ), m)
+        ind, m_arg = self._n(count, m)
+        self._enqueue("rt_connect_paths", stream, _ptr(pb), n, _ptr(con), _ptr(idx), _ptr(occ), m_arg, form=ind)
 
-    def retire(self, paths, samples, stream=None):
+    def retire(self, paths, samples, stream=None, count=None):
         """rt_retire_paths: samples[tag] = (radiance, 1) for every path that is not ALIVE and whose
         tag is below len(samples); `samples` is a (tags, 4) float32 tensor.  Enqueued on `stream`
-        without a host wait."""
+        without a host wait.  count: as in trace."""
         pb = self._records(paths.buffer if isinstance(paths, Paths) else paths, "paths", 12)
         sm = self._records(samples, "samples", 4)
-        self._enqueue("rt_retire_paths", stream, _ptr(pb), pb.shape[0], _ptr(sm), sm.shape[0])
+        ind, n_arg = self._n(count, pb.shape[0])
+        self._enqueue("rt_retire_paths", stream, _ptr(pb), n_arg, _ptr(sm), sm.shape[0], form=ind)
 
     def average(self, samples, spp, out=None, stream=None):
         """rt_average_samples: (pixels * spp, 4) float32 samples, a pixel's spp samples side by
@@ -604,7 +646,57 @@ class RendererQueries:
         self._pt_buffers = b
         return b
 
-    def path_trace(self, spp=None, max_bounces=None, shading_mode=None, stream=0, batch_samples=True):
+    def _device_rounds(self, B, guard, lookahead, mode, mb, stream, ts):
+        """path_trace's rounds over one group of camera paths with every count on the device.
+        B["words"] is two (alive, shadow) pairs: round r reads its alive count from pair `cur` and
+        writes the next alive count and its shadow count into the other pair, which one 8-byte
+        copy then takes to row r of the pinned B["rows"], followed by event r.  Before round r is
+        enqueued the host waits for event r - 1 - lookahead and reads that row: alive 0 ends the
+        loop (the rounds enqueued past it ran on count 0 and changed nothing), anything else is
+        the new host bound of the arrays (counts never grow).  Returns (closest rays, shadow rays,
+        rounds that had a count, host waits)."""
+        import torch
+        A, SH = Paths.ALIVE, Paths.SHADOW
+        W, rows, events = B["words"], B["rows"], B["events"]
+        q = dict(stream=stream)
+        n = B["cap"]
+        with torch.cuda.stream(ts):
+            W[0, 0:1].fill_(n)
+        cur, r, closest, shadows = 0, 0, n, 0
+        while True:
+            j = r - 1 - lookahead
+            if j >= 0:
+                events[j].synchronize()
+                alive, ns = int(rows[j, 0]), int(rows[j, 1])
+                shadows += ns
+                if alive == 0:
+                    return closest, shadows, j + 1, j + 1
+                if j + 1 >= guard:
+                    raise RuntimeError(f"a path outlived the renderer's longest ({guard} steps)")
+                closest += alive
+                n = alive
+            c_in, c_alive, c_shadow = W[cur, 0:1], W[1 - cur, 0:1], W[1 - cur, 1:2]
+            rays, pb = B["rays"][cur][:n], B["paths"][cur][:n]
+            nxt, shadow, contrib = B["nxt"][:n], B["shadow"][:n], B["contrib"][:n]
+            hits = self.trace(rays, out=B["hits"][:n], count=c_in, **q)
+            S = self.resolve(rays, hits, out=(B["surf"][:n], B["mat"][:n]), count=c_in, **q)
+            self.shade(rays, S, pb, shading_mode=mode, max_bounces=mb, out=(nxt, shadow, contrib), count=c_in, **q)
+            self.compact(pb, SH, (shadow,), out=Compacted(c_shadow, B["sh_index"][:n], [B["shadow_c"][:n]], B["pinned"][0], None),
+                         count=c_in, **q)
+            self.trace(B["shadow_c"][:n], any_hit=True, out=B["occluded"][:n], count=c_shadow, **q)
+            self.connect(pb, contrib, B["occluded"][:n], index=B["sh_index"][:n], m=n, count=c_shadow, **q)
+            self.retire(pb, B["samples"], count=c_in, **q)
+            self.compact(pb, A, (nxt, pb), index=False,
+                         out=Compacted(c_alive, None, [B["rays"][1 - cur][:n], B["paths"][1 - cur][:n]], B["pinned"][1],
+                                       None),
+                         count=c_in, **q)
+            with torch.cuda.stream(ts):
+                rows[r].copy_(W[1 - cur], non_blocking=True)
+            events[r].record(ts)
+            cur, r = 1 - cur, r + 1
+
+    def path_trace(self, spp=None, max_bounces=None, shading_mode=None, stream=0, batch_samples=True, device_counts=False,
+                   lookahead=1):
         """Frame 0 of the current uniforms from queries only: camera_paths, then per round
         trace -> resolve -> shade -> compact(SHADOW: shadow rays + index) -> trace(any_hit) ->
         connect -> retire -> compact(ALIVE: next rays + paths) until no path is left, then
@@ -613,9 +705,21 @@ class RendererQueries:
         image in one array (tag = pixel * spp + s), else one sample at a time.  Runs on `stream`
         (default 0 = torch's default stream); the working buffers are allocated once per size and
         kept.  Returns the (H, W, 4) float32 tensor, valid on that stream; the ray totals are kept
-        in `last_path_trace` (closest_rays, shadow_rays, paths, rounds)."""
+        in `last_path_trace` (closest_rays, shadow_rays, paths, rounds).
+
+        device_counts=True runs the same rounds through the count= forms: every launch takes its
+        count from the device, sized on the host by the newest alive count the host has seen, and
+        per round one 8-byte copy of (alive, shadow) and one event go to the host.  The host waits
+        for the event of round r - 1 - lookahead before it enqueues round r, and stops when that
+        round left no path: `lookahead` rounds are in flight beyond the one waited for, and at the
+        end as many run on a count of 0.  lookahead=0 waits once per round.  Needs a stream torch
+        can name (not None).  Same image, same totals; last_path_trace gains host_waits (event
+        waits; as `rounds`, of the group of samples that took the most)."""
         import torch
         dev = self._device()
+        lookahead = int(lookahead)
+        if device_counts and (stream is None or lookahead < 0):
+            raise ValueError("device_counts needs a stream handle (0 = torch's default) and lookahead >= 0")
         spp = int(self.samplesPerPixel if spp is None else spp)
         mb = int(self.maxBounces if max_bounces is None else max_bounces)
         mode = int(self.shadingMode if shading_mode is None else shading_mode)
@@ -629,6 +733,10 @@ class RendererQueries:
         with torch.cuda.stream(ts if ts is not None else torch.cuda.current_stream(dev)):
             B = self._path_buffers(pixels * spp if batch_samples else pixels, pixels * spp)
             image = torch.empty((pixels, 4), dtype=torch.float32, device=dev)
+            if device_counts and (B.get("rows") is None or B["rows"].shape[0] != guard + lookahead):
+                B["words"] = torch.zeros((2, 2), dtype=torch.int32, device=dev)
+                B["rows"] = torch.zeros((guard + lookahead, 2), dtype=torch.int32, pin_memory=True)
+                B["events"] = [torch.cuda.Event() for _ in range(guard + lookahead)]
         A, SH = Paths.ALIVE, Paths.SHADOW
         q = dict(stream=stream)
         totals = dict(closest_rays=0, shadow_rays=0, paths=pixels * spp, rounds=0)
@@ -638,6 +746,13 @@ class RendererQueries:
                 k = s * pixels if batch_samples else 0
                 self.camera_paths(s, uniforms=u, tag_stride=spp, tag_offset=s,
                                   out=(B["rays"][cur][k:k + pixels], B["paths"][cur][k:k + pixels]), **q)
+            if device_counts:
+                nc, ns, rounds, waits = self._device_rounds(B, guard, lookahead, mode, mb, stream, ts)
+                totals["closest_rays"] += nc
+                totals["shadow_rays"] += ns
+                totals["rounds"] = max(totals["rounds"], rounds)
+                totals["host_waits"] = max(totals.get("host_waits", 0), waits)
+                continue
             n, rounds = B["cap"], 0
             while n > 0:
                 if rounds >= guard:

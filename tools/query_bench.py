@@ -39,7 +39,11 @@ timed runs each child does one counting run for the node visits and triangle tes
     compaction form; and Renderer.draw (rt_render_frame) for scale.  Each is timed by the wall
     clock around one frame that ends with a device synchronisation, median of five after two
     warm-up runs; rate = (closest-hit + shadow rays of the frame) / time.  The three query images
-    are compared bit for bit.  Then rt_compact_paths alone on round 0's records of path_trace's
+    are compared bit for bit.  Beside them the device-count leg: Renderer.path_trace(device_counts=
+    True) at look-ahead 0, 1 and 2 (every launch's count read on the device, one event wait per
+    round `lookahead` rounds behind the enqueue), timed the same way in the same session, its image
+    compared with the loop's bit for bit (loop_device_ms / loop_device_grays per look-ahead,
+    loop_device_host_waits).  Then rt_compact_paths alone on round 0's records of path_trace's
     batch, in the loop's two shapes (SHADOW: shadow rays + index; ALIVE: next rays + paths), timed by
     HIP events on a stream of its own (median of five after two), as a share of its HBM floor at
     6.3 TB/s: every line of `paths` read once for the flag words (48 n), the selection words
@@ -279,6 +283,7 @@ def glue_render(rt, R, spp, max_bounces, compact):
     return total / float(spp), closest, shadow
 
 
+LOOKAHEADS = (0, 1, 2)   # the device-count leg of --loop
 COMPACT_SHAPES = {"shadow": (2, (2,), True), "alive": (1, (2, 3), False)}   # mask, stream words, index
 
 
@@ -309,7 +314,17 @@ def child_loop(args):
         images["glue_compact" if compact else "glue_carry"] = img
         return nc + ns
 
-    for kind, fn in (("frame", frame), ("loop", loop), ("glue_carry", lambda: glue(False)), ("glue_compact", lambda: glue(True))):
+    waits = {}
+
+    def loop_device(la):
+        images[f"loop_device{la}"] = R.path_trace(device_counts=True, lookahead=la)
+        t = R.last_path_trace
+        waits[la] = t["host_waits"]
+        return t["closest_rays"] + t["shadow_rays"]
+
+    legs = [("frame", frame), ("loop", loop), ("glue_carry", lambda: glue(False)), ("glue_compact", lambda: glue(True))]
+    legs += [(f"loop_device{la}", lambda la=la: loop_device(la)) for la in LOOKAHEADS]
+    for kind, fn in legs:
         for k in range(WARMUP + RUNS):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -319,7 +334,9 @@ def child_loop(args):
     rgb = images["loop"].reshape(-1, 4)[:, 0:3].contiguous().view(torch.int32)
     _emit(images=True, equal=bool(torch.equal(rgb, images["glue_carry"].contiguous().view(torch.int32))
                                   and torch.equal(rgb, images["glue_compact"].contiguous().view(torch.int32))),
-          rounds=R.last_path_trace["rounds"])
+          device_equal=all(torch.equal(images["loop"].view(torch.int32), images[f"loop_device{la}"].view(torch.int32))
+                           for la in LOOKAHEADS),
+          rounds=R.last_path_trace["rounds"], host_waits={str(la): waits[la] for la in LOOKAHEADS})
     # round 0 of the batch: every sample's camera paths, traced, resolved and shaded once
     del images
     R._pt_buffers = None
@@ -395,7 +412,8 @@ def main_loop(args):
                      "ending in a device synchronisation, Grays/s = (closest-hit + shadow rays) / time; compactions by "
                      f"HIP events around the call on its stream, floor at {HBM_BYTES_PER_S / 1e12} TB/s"}
     lines, err = run_child("loop", args)
-    legs = ["frame", "loop", "glue_carry", "glue_compact"] + ["compact_" + k for k in COMPACT_SHAPES]
+    legs = (["frame", "loop", "glue_carry", "glue_compact"] + [f"loop_device{la}" for la in LOOKAHEADS]
+            + ["compact_" + k for k in COMPACT_SHAPES])
     for kind in legs:
         runs = [r for r in lines if r.get("kind") == kind and r["run"] >= WARMUP]
         if not err and len(runs) != RUNS:
@@ -424,6 +442,13 @@ def main_loop(args):
         if r.get("images"):
             res["query_images_bit_equal"] = r["equal"]
             res["loop_rounds"] = r["rounds"]
+            res["loop_device_images_bit_equal"] = r["device_equal"]
+            res["loop_device_host_waits"] = r["host_waits"]
+    # the device-count leg, keyed by look-ahead
+    for key in ("ms", "runs_ms", "rays", "grays", "runs_grays"):
+        res[f"loop_device_{key}"] = {str(la): res.pop(f"loop_device{la}_{key}") for la in LOOKAHEADS}
+    res["loop_device_over_loop"] = {str(la): round(res["loop_device_grays"][str(la)] / res["loop_grays"], 4)
+                                    for la in LOOKAHEADS}
     best = max(res["glue_carry_grays"], res["glue_compact_grays"])
     res["loop_over_best_glue"] = round(res["loop_grays"] / best, 4)
     print(json.dumps(res))
