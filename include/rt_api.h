@@ -830,6 +830,57 @@ rt_status rt_debug_camera_paths_host(const Uniforms* u, const rt_camera_opts* op
 rt_status rt_debug_compact_paths_host(const rt_path* paths, uint32_t n, uint32_t mask, const rt_compact_stream* streams,
                                       uint32_t stream_count, uint32_t* index, uint32_t* count);
 
+/* Test hooks (host only, no device): what every frame after the first adds to the path queries'
+ * loop, as per-record code compiled for the host over HOST pointers (no device query of theirs
+ * exists yet).  The arithmetic is the frame kernels' own functions: depth and motion of sample 0's
+ * bounce-0 hits (Raytracing.metal:342-389), the motion-adaptive extra samples (:777-789), the
+ * resolve with the accumulation against the history (:792-819).  Frames assembled from these hooks
+ * and the ones above equal the oracle's bit for bit in radiance, depth and motion.
+ *
+ * rt_debug_primary_outputs_host: called before the shade hook of the same round, so `paths` holds
+ * the state at the hit.  A record is used when RT_PATH_ALIVE is set, bounce == 0, its tag is
+ * selected by `opts` and the hit's `triangle` is below the scene's triangle count; depth[pixel] and
+ * motion[pixel] (two fp32 per pixel, as rt_read_aux returns them) then get what the renderer
+ * computes from the hit's triangle, u and v, u->camera and u->previousCamera.  Every other record
+ * writes nothing.  Once per round, in order, gives the renderer's "last bounce-0 hit of sample 0
+ * wins" for glass paths.  The scene is a description (checked as rt_scene_upload checks it) with
+ * the previous instance transforms, one per mesh (NULL = the current ones); its previous positions
+ * are the current positions.  A pixel the renderer's sample 0 never hits keeps depth 1.0e8f and
+ * motion (0, 0): the caller's fill.
+ *
+ * rt_debug_extra_paths_host: maxExtra is rt_camera_paths' definition.  For pixel pix =
+ * opts->first_pixel + i: extra[i] = the renderer's extra-sample count from motion[pix] and
+ * motion_prev[pix] (NULL: zeros).  For j < maxExtra, record i * maxExtra + j of rays / paths is the
+ * rt_camera_paths record of sample opts->sample + j (the caller passes samplesPerPixel) with tag
+ * pix * tag_stride + tag_offset + j when j < extra[i], otherwise zero-filled with flags 0 and
+ * tmax = -1.  With maxExtra == 0 only `extra` is written; rays and paths may be NULL.
+ * random_offsets is required; otherwise rt_camera_paths' checks.
+ *
+ * rt_debug_resolve_samples_host: with spp = u->samplesPerPixel and e = extra ? extra[p] : 0 (an e
+ * above sample_stride - spp counts as that), total = the first spp + e samples of pixel p summed
+ * in sample order / their number; when u->frameIndex > 0, mixed with history[p] by the renderer's
+ * motion-adaptive history weight (a NULL motion target reads as zeros).  Alpha 1.0f.  At frame 0
+ * with extra == NULL and sample_stride == spp: rt_average_samples' arithmetic.
+ * RT_ERR_INVALID_ARG: history == NULL with frameIndex > 0, spp outside 1 .. 64,
+ * spp + maxExtra > sample_stride, rgba == history or samples.
+ * Alignment: record arrays, samples, history, rgba 16-byte; motion targets 8-byte; others 4-byte. */
+typedef struct rt_target_opts {   /* 32 B */
+    uint32_t tag_stride;          /* >= 1: pixel = tag / tag_stride */
+    uint32_t tag_offset;          /* a record is selected when tag % tag_stride == tag_offset (sample 0's) */
+    uint32_t pixels;              /* depth / motion hold this many pixels; a pixel at or above it is skipped */
+    uint32_t reserved[5];
+} rt_target_opts;
+RT_STATIC_ASSERT(sizeof(rt_target_opts) == 32, "rt_target_opts is 32 B");
+rt_status rt_debug_primary_outputs_host(const rt_scene_desc* scene, const rt_packed_float4x3* prev_transforms,
+                                        const Uniforms* u, const rt_target_opts* opts, const rt_ray_hit* hits,
+                                        const rt_path* paths, uint32_t n, float* depth, float* motion);
+rt_status rt_debug_extra_paths_host(const Uniforms* u, const rt_camera_opts* opts, const uint32_t* random_offsets,
+                                    const float* motion, const float* motion_prev, uint32_t n, rt_ray* rays, rt_path* paths,
+                                    uint32_t* extra);
+rt_status rt_debug_resolve_samples_host(const Uniforms* u, const float* samples, uint32_t sample_stride,
+                                        const uint32_t* extra, const float* motion, const float* motion_prev,
+                                        const float* history, uint32_t pixels, float* rgba);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@ from ._abi import (TEXTURE_SLOTS, Tuning, Camera, Float3, Light, MaterialOverrid
                    f3)
 # the device queries live in queries.py; every public name of it is the package's too
 from .queries import (Hits, Surface, Paths, Shaded, Compacted, RendererQueries, _shade_opts, _camera_opts,
-                      debug_trace_host, debug_resolve_host, debug_shade_host, debug_camera_paths_host)
+                      debug_trace_host, debug_resolve_host, debug_shade_host, debug_camera_paths_host,
+                      debug_primary_outputs_host, debug_extra_paths_host, debug_resolve_samples_host)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librt_hip.so")

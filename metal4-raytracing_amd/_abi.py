@@ -255,6 +255,10 @@ class DeviceCount(C.Structure):  # rt_device_count: 16 B
     _fields_ = [("count", C.c_void_p), ("max", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class TargetOpts(C.Structure):  # rt_target_opts: 32 B
+    _fields_ = [("tag_stride", C.c_uint32), ("tag_offset", C.c_uint32), ("pixels", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
 class QueryStats(C.Structure):  # rt_query_stats
     _fields_ = [
         ("rays", C.c_uint64),
@@ -329,6 +333,7 @@ EXPORTED_SYMBOLS = [
     "rt_connect_paths_on_indirect", "rt_retire_paths_indirect", "rt_retire_paths_on_indirect",
     "rt_version", "rt_debug_trace_host", "rt_debug_resolve_host", "rt_debug_shade_host",
     "rt_debug_camera_paths_host", "rt_debug_compact_paths_host",
+    "rt_debug_primary_outputs_host", "rt_debug_extra_paths_host", "rt_debug_resolve_samples_host",
     # rt_scene.h
     "rt_material_override_glass", "rt_scene_new", "rt_scene_free", "rt_scene_last_error",
     "rt_scene_add_obj", "rt_scene_add_usd", "rt_scene_add_procedural", "rt_scene_set_lights", "rt_scene_set_light_intensity",
@@ -401,6 +406,9 @@ def declare(lib):
         "rt_connect_paths": (st, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32]),
         "rt_retire_paths": (st, [vp, vp, C.c_uint32, vp, C.c_uint32]),
         "rt_average_samples": (st, [vp, vp, C.c_uint32, C.c_uint32, vp]),
+        "rt_debug_primary_outputs_host": (st, [P(SceneDesc), vp, P(Uniforms), P(TargetOpts), vp, vp, C.c_uint32, vp, vp]),
+        "rt_debug_extra_paths_host": (st, [P(Uniforms), P(CameraOpts), vp, vp, vp, C.c_uint32, vp, vp, vp]),
+        "rt_debug_resolve_samples_host": (st, [P(Uniforms), vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp]),
         "rt_version": (C.c_char_p, []),
         "rt_debug_trace_host": (st, [P(SceneDesc), P(C.c_float), P(C.c_float), C.c_uint32, C.c_int32, P(C.c_float),
                                      P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32)]),

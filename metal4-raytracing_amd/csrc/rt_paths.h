@@ -2,20 +2,28 @@
 // rt_connect_paths, rt_retire_paths, rt_average_samples) and the tile geometry of
 // rt_compact_paths.  One text for the kernels (rq_camera .. rq_average, rt_query.hip) and the host
 // hooks (rt_paths_host.cpp), as rt_scatter.h is for the shading query: same function, same
-// operands, so the floats are equal bit for bit by construction.
+// operands, so the floats are equal bit for bit by construction.  Also the per-record code of the
+// temporal hooks (rt_debug_primary_outputs_host, rt_debug_extra_paths_host,
+// rt_debug_resolve_samples_host): record selection and layout around the frames' own arithmetic
+// (rt_shade.h), written host / device like the rest; only the hooks call it so far.
 #pragma once
+#include "rt_shade.h"     // primary_outputs, extra_samples, resolve_pixel: the frames' own arithmetic
 #include "rt_surface.h"   // ldf3, f2u / u2f
 
 namespace rt {
 
 // ---- camera paths ----------------------------------------------------------------------------------
+// The most extra samples a pixel can take (Raytracing.metal:777-779): the stride of the Halton
+// indices and of the temporal hooks' tags counts them whether a pixel takes them or not.
+RT_HD int max_extra_samples(const Uniforms& U) {
+    return (U.enableMotionAdaptiveSampling != 0 && U.motionSamplingMaxExtraSamples > 0) ? U.motionSamplingMaxExtraSamples : 0;
+}
+
 // Halton index of sample s of a pixel whose random offset is rnd: base_hidx of rt_wavefront.hip
 // (Raytracing.metal:263-270) in unsigned arithmetic, the same bits.
 RT_HD uint32_t camera_hidx(const Uniforms& U, uint32_t rnd, int s) {
     const int spp = U.samplesPerPixel > 1 ? U.samplesPerPixel : 1;
-    const int maxExtra = (U.enableMotionAdaptiveSampling != 0 && U.motionSamplingMaxExtraSamples > 0)
-                             ? U.motionSamplingMaxExtraSamples : 0;
-    return rnd + (U.frameIndex * ((uint32_t)spp + (uint32_t)maxExtra) + (uint32_t)s);
+    return rnd + (U.frameIndex * ((uint32_t)spp + (uint32_t)max_extra_samples(U)) + (uint32_t)s);
 }
 
 // rt_ray and rt_path of a camera path as 16-B words.
@@ -64,6 +72,69 @@ RT_HD float4 average_pixel(const float4* s, uint32_t spp) {
     for (uint32_t k = 1; k < spp; ++k) total = total + ld3(s[k]);
     total = total / (float)spp;
     return make_float4(total.x, total.y, total.z, 1.0f);
+}
+
+// ---- temporal hooks: depth / motion, extra samples, the EMA -------------------------------------------
+// Which records rt_debug_primary_outputs_host uses, from the path's flags / bounce / tag words alone (read
+// before anything else of the record): a live path at bounce 0 whose tag is sample `offset` of a
+// pixel below `pixels`.  The renderer's `bounce == 0 && sampleIndex == 0` (Raytracing.metal:342).
+RT_HD bool primary_selected(uint32_t flags, int bounce, uint32_t tag, uint32_t stride, uint32_t offset, uint32_t pixels,
+                            uint32_t& pix) {
+    if ((flags & RT_PATH_ALIVE) == 0u || bounce != 0) return false;
+    pix = tag / stride;
+    return tag - pix * stride == offset && pix < pixels;
+}
+
+// Depth and motion of a selected record's hit (h0: t, u, v, triangle): primary_outputs itself.
+// False for a miss or a triangle the scene does not have; nothing is indexed then.
+RT_HD bool primary_record(const DevScene& S, const Uniforms& U, const float4 h0, float& depth, f2& motion) {
+    const uint32_t id = f2u(h0.w);
+    if (id >= (uint32_t)S.num_tris) return false;
+    primary_outputs(S, U, id, h0.y, h0.z, depth, motion);
+    return true;
+}
+
+// Two floats of a motion target as f2; a null target reads as zeros (the targets after rt_resize).
+RT_HD f2 ld2(const float2* a, size_t i) {
+    f2 r;
+    r.x = r.y = 0.0f;
+    if (a) {
+        const float2 v = a[i];
+        r.x = v.x;
+        r.y = v.y;
+    }
+    return r;
+}
+
+// Extra samples of a pixel from this frame's and the previous frame's motion: extra_samples itself.
+RT_HD int extra_count(const Uniforms& U, f2 mv, f2 pm) { return extra_samples(U, max_extra_samples(U), mv, pm); }
+
+// The record of an extra sample a pixel does not take: what rt_shade_hits writes for a ray that
+// is not to be traced (zeros, flags 0, tmax = -1).
+RT_HD void camera_record_none(CameraWords& w) {
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    w.r0 = z;
+    w.r1 = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    w.p0 = z;
+    w.p1 = z;
+    w.p2 = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// Samples pixel p of rt_debug_resolve_samples_host holds: spp + extra[p] (extra null: none), at most its stride.
+RT_HD uint32_t pixel_samples(const uint32_t* extra, size_t p, uint32_t spp, uint32_t stride) {
+    const uint32_t e = extra ? extra[p] : 0u;
+    return e < stride - spp ? spp + e : stride;   // spp <= stride (checked by the host)
+}
+
+// A pixel of rt_debug_resolve_samples_host: its `count` samples at s summed in sample order, then
+// resolve_pixel (the division and, past frame 0, the EMA against history[pix] weighted by the
+// motion); alpha 1 as the frame kernels store it.
+RT_HD float4 resolve_samples_pixel(const Uniforms& U, const float4* s, uint32_t count, f2 mv, f2 pm, const float4* history,
+                                   size_t pix) {
+    f3 total = ld3(s[0]);
+    for (uint32_t k = 1; k < count; ++k) total = total + ld3(s[k]);
+    const f3 c = resolve_pixel(U, total, (int)count, mv, pm, history, pix);
+    return make_float4(c.x, c.y, c.z, 1.0f);
 }
 
 // ---- compaction: tile geometry ------------------------------------------------------------------------

@@ -121,6 +121,51 @@ inline rt_status validate_compact(rt_ctx* c, const void* paths, uint32_t n, uint
     return RT_OK;
 }
 
+// What the temporal host hooks accept (the scene apart).
+inline rt_status validate_primary(rt_ctx* c, const Uniforms* u, const rt_target_opts* o, const void* hits, const void* paths,
+                                  uint32_t n, const void* depth, const void* motion) {
+    if (!u || !o) FAIL(c, RT_ERR_INVALID_ARG, "null uniforms / opts");
+    if (o->tag_stride == 0) FAIL(c, RT_ERR_INVALID_ARG, "tag_stride is 0");
+    if (o->tag_offset >= o->tag_stride) FAIL(c, RT_ERR_INVALID_ARG, "tag_offset is not below tag_stride");
+    if (n > 0 && (!hits || !paths || !depth || !motion)) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+    if ((((uintptr_t)hits | (uintptr_t)paths) & 15u) || ((uintptr_t)motion & 7u) || ((uintptr_t)depth & 3u))
+        FAIL(c, RT_ERR_INVALID_ARG, "hits and paths must be 16-byte aligned, motion 8-byte, depth 4-byte");
+    return RT_OK;
+}
+// rt_camera_paths' checks, but that rays / paths may be null when no pixel can take an extra sample
+// (max_extra: max_extra_samples of u, 0 for a null u).
+inline rt_status validate_extra(rt_ctx* c, const Uniforms* u, const rt_camera_opts* o, const void* random_offsets,
+                                const void* motion, const void* motion_prev, uint32_t n, const void* rays, const void* paths,
+                                const void* extra, int max_extra) {
+    if (rt_status st = validate_camera(c, u, o, random_offsets, 0, rays, paths)) return st;
+    if ((uint64_t)o->first_pixel + n > (uint64_t)u->width * (uint64_t)u->height)
+        FAIL(c, RT_ERR_INVALID_ARG, "first_pixel + n is past the image");
+    if (n > 0 && (!motion || !extra)) FAIL(c, RT_ERR_INVALID_ARG, "null motion / extra");
+    if (n > 0 && max_extra > 0 && (!rays || !paths)) FAIL(c, RT_ERR_INVALID_ARG, "null rays / paths with extra samples enabled");
+    if ((((uintptr_t)motion | (uintptr_t)motion_prev) & 7u) || ((uintptr_t)extra & 3u))
+        FAIL(c, RT_ERR_INVALID_ARG, "motion targets must be 8-byte aligned, extra 4-byte aligned");
+    if (u->samplesPerPixel > 4096 || max_extra > 4096) FAIL(c, RT_ERR_INVALID_ARG, "bad spp");   // as rt_render_frame
+    if (o->sample > 0x7fffffff - max_extra) FAIL(c, RT_ERR_INVALID_ARG, "sample + the most extra samples overflows");
+    return RT_OK;
+}
+inline rt_status validate_resolve_samples(rt_ctx* c, const Uniforms* u, const void* samples, uint32_t stride,
+                                          const void* extra, const void* motion, const void* motion_prev, const void* history,
+                                          uint32_t pixels, const void* rgba, int max_extra) {
+    if (!u) FAIL(c, RT_ERR_INVALID_ARG, "null uniforms");
+    if (u->samplesPerPixel < 1 || u->samplesPerPixel > 64) FAIL(c, RT_ERR_INVALID_ARG, "samplesPerPixel outside 1 .. 64");
+    if ((uint64_t)u->samplesPerPixel + (uint64_t)max_extra > (uint64_t)stride)
+        FAIL(c, RT_ERR_INVALID_ARG, "samplesPerPixel + the most extra samples is more than sample_stride");
+    if (u->frameIndex > 0 && !history) FAIL(c, RT_ERR_INVALID_ARG, "null history past frame 0");
+    if (pixels > 0) {
+        if (!samples || !rgba) FAIL(c, RT_ERR_INVALID_ARG, "null argument");
+        if (rgba == history || rgba == samples) FAIL(c, RT_ERR_INVALID_ARG, "in place is not supported");
+    }
+    if ((((uintptr_t)samples | (uintptr_t)history | (uintptr_t)rgba) & 15u) ||
+        (((uintptr_t)motion | (uintptr_t)motion_prev) & 7u) || ((uintptr_t)extra & 3u))
+        FAIL(c, RT_ERR_INVALID_ARG, "samples, history and rgba must be 16-byte aligned, motion targets 8-byte, extra 4-byte");
+    return RT_OK;
+}
+
 // A scene description flattened mesh by mesh: positions and normals with every mesh's vertices
 // after the previous one's, triangles as (three vertex ids, mesh << 8 | submesh), 12 floats of
 // transform per mesh.  nrm may be null.

@@ -120,8 +120,11 @@ __host__ __device__ __forceinline__ bool needs_full(const Uniforms& U, const Dev
 // Depth and motion vector of a bounce-0 hit of sample 0 (Raytracing.metal:342-389): the hit
 // point through this frame's and the previous frame's instance transforms and cameras.  Inline in
 // the per-pixel kernel; the wavefront kernels record the hit and wf_motion evaluates this once
-// per pixel after the pass (the last bounce-0 hit of sample 0 wins either way).
-__device__ __forceinline__ void primary_outputs(const DevScene& S, const Uniforms& U, uint32_t id, float bu, float bv,
+// per pixel after the pass (the last bounce-0 hit of sample 0 wins either way).  This function,
+// extra_samples and resolve_pixel below are also, compiled for the host, the arithmetic of the
+// temporal test hooks (rt_paths.h, rt_paths_host.cpp): S then carries tri_info, pos / prev_pos and
+// inst / prev_inst only, as host pointers.
+__host__ __device__ __forceinline__ void primary_outputs(const DevScene& S, const Uniforms& U, uint32_t id, float bu, float bv,
                                                 float& depth_out, f2& motion_out) {
     const uint4 ti = S.tri_info[id];
     const int instanceIndex = (int)(ti.w >> 8);
@@ -246,7 +249,7 @@ __device__ __forceinline__ void primary_ray(const Uniforms& U, const ShadeTabs& 
 }
 
 // Motion-adaptive extra samples after sample 0 (Raytracing.metal:779-789).
-__device__ __forceinline__ int extra_samples(const Uniforms& U, int maxExtra, f2 mv, f2 pm) {
+__host__ __device__ __forceinline__ int extra_samples(const Uniforms& U, int maxExtra, f2 mv, f2 pm) {
     float motionMag = fmaxf(sqrtf(mv.x * mv.x + mv.y * mv.y), sqrtf(pm.x * pm.x + pm.y * pm.y));
     float low = fmaxf(U.motionSamplingLowThresholdPixels, 0.0f);
     float high = fmaxf(U.motionSamplingHighThresholdPixels, low + 1e-3f);
@@ -256,7 +259,7 @@ __device__ __forceinline__ int extra_samples(const Uniforms& U, int maxExtra, f2
 }
 
 // Average + temporal EMA (Raytracing.metal:792-817).
-__device__ __forceinline__ f3 resolve_pixel(const Uniforms& U, f3 total, int totalSamples, f2 mv, f2 pm,
+__host__ __device__ __forceinline__ f3 resolve_pixel(const Uniforms& U, f3 total, int totalSamples, f2 mv, f2 pm,
                                             const float4* accum_in, size_t pix) {
     total = total / (float)max(totalSamples, 1);
     if (U.frameIndex > 0) {

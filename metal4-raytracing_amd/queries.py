@@ -4,8 +4,10 @@ Every query (rt_trace_closest / rt_trace_any, rt_resolve_hits, rt_shade_hits, rt
 rt_compact_paths, rt_connect_paths, rt_retire_paths, rt_average_samples) goes through the same
 few helpers of RendererQueries: one device record check, one host staging, one `out=` check, one
 enqueue.  The six whose record count a compaction produces take `count=`: the count stays on the
-device and the call goes to the entry point's _indirect form (rt_device_count).  The package
-re-exports every public name of this module.
+device and the call goes to the entry point's _indirect form (rt_device_count).  The temporal
+hooks (debug_primary_outputs_host, debug_extra_paths_host, debug_resolve_samples_host) are host
+test hooks only: no device query of theirs exists yet.  The package re-exports every public name
+of this module.
 """
 import ctypes as C
 
@@ -226,6 +228,82 @@ def debug_camera_paths_host(uniforms, random_offsets, sample, first_pixel=0, n=N
     _check(_lib().rt_debug_camera_paths_host(C.byref(uniforms), C.byref(o), rnd.ctypes.data, n, rays.ctypes.data,
                                              p.ctypes.data))
     return rays, Paths(p, p.view(np.int32))
+
+
+def debug_primary_outputs_host(scene, uniforms, hits, paths, depth, motion, tag_stride=1, tag_offset=0,
+                               prev_transforms=None):
+    """Test hook rt_debug_primary_outputs_host: depth and motion of sample 0's bounce-0 hits, over a scene
+    description whose previous positions are its positions.  hits: a Hits or its (n, 8) float32
+    buffer; paths: a Paths or its (n, 12) buffer; depth (pixels elements) and motion (pixels x 2)
+    are float32 numpy arrays updated IN PLACE; prev_transforms: (meshes, 4, 3) packed previous
+    instance transforms, None = the current ones.  Returns (depth, motion)."""
+    h = np.ascontiguousarray(hits.buffer if isinstance(hits, Hits) else hits).reshape(-1, 8)
+    pb = paths.buffer if isinstance(paths, Paths) else paths
+    p = np.ascontiguousarray(pb).reshape(-1, 12)
+    if h.dtype != np.float32 or p.dtype != np.float32 or h.shape[0] != p.shape[0]:
+        raise ValueError("hits must be float32 (n, 8) and paths float32 (n, 12) records of one n")
+    for name, x, per in (("depth", depth, 1), ("motion", motion, 2)):
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float32 and x.flags.c_contiguous and x.size == depth.size * per):
+            raise ValueError(f"{name} must be a contiguous float32 array of pixels x {per} elements")
+    d_ = scene.desc() if hasattr(scene, "desc") else scene
+    pt = None
+    if prev_transforms is not None:
+        pt = np.ascontiguousarray(prev_transforms, np.float32).reshape(-1, 12)
+        if pt.shape[0] != d_.mesh_count:
+            raise ValueError(f"{d_.mesh_count} meshes but {pt.shape[0]} previous transforms")
+    o = _abi.TargetOpts()
+    o.tag_stride, o.tag_offset, o.pixels = int(tag_stride), int(tag_offset), depth.size
+    _check(_lib().rt_debug_primary_outputs_host(C.byref(d_), pt.ctypes.data if pt is not None else None, C.byref(uniforms),
+                                                C.byref(o), h.ctypes.data, p.ctypes.data, h.shape[0], depth.ctypes.data,
+                                                motion.ctypes.data))
+    return depth, motion
+
+
+def debug_extra_paths_host(uniforms, random_offsets, motion, motion_prev=None, sample=None, first_pixel=0, n=None,
+                           tag_stride=1, tag_offset=0):
+    """Test hook rt_debug_extra_paths_host: the motion-adaptive extra samples.  motion / motion_prev:
+    float32 arrays of width * height * 2 elements (motion_prev None = zeros).  Returns ((n *
+    maxExtra, 8) rays, Paths, (n,) uint32 extra) as numpy arrays."""
+    pixels = uniforms.width * uniforms.height
+    rnd = np.ascontiguousarray(random_offsets, np.uint32).reshape(-1)
+    if rnd.shape[0] != pixels:
+        raise ValueError(f"random_offsets must hold {pixels} words, not {rnd.shape[0]}")
+    mv = np.ascontiguousarray(motion, np.float32).reshape(-1)
+    pm = None if motion_prev is None else np.ascontiguousarray(motion_prev, np.float32).reshape(-1)
+    if mv.shape[0] != 2 * pixels or (pm is not None and pm.shape[0] != 2 * pixels):
+        raise ValueError(f"motion targets must hold {pixels} x 2 floats")
+    if n is None:
+        n = max(pixels - first_pixel, 0)
+    me = max(int(uniforms.motionSamplingMaxExtraSamples), 0) if uniforms.enableMotionAdaptiveSampling else 0
+    rays, p, extra = np.empty((n * me, 8), np.float32), np.empty((n * me, 12), np.float32), np.empty(n, np.uint32)
+    o = _camera_opts(uniforms.samplesPerPixel if sample is None else sample, first_pixel, tag_stride, tag_offset)
+    _check(_lib().rt_debug_extra_paths_host(C.byref(uniforms), C.byref(o), rnd.ctypes.data, mv.ctypes.data,
+                                            pm.ctypes.data if pm is not None else None, n, rays.ctypes.data, p.ctypes.data,
+                                            extra.ctypes.data))
+    return rays, Paths(p, p.view(np.int32)), extra
+
+
+def debug_resolve_samples_host(uniforms, samples, sample_stride, extra=None, motion=None, motion_prev=None, history=None):
+    """Test hook rt_debug_resolve_samples_host: the renderer's resolve of any frame.  samples:
+    (pixels * sample_stride, 4) float32; extra: (pixels,) uint32 or None; motion, motion_prev:
+    pixels x 2 floats or None (zeros); history: pixels x 4 floats, required past frame 0.  Returns
+    the (pixels, 4) float32 array."""
+    s = np.ascontiguousarray(samples, np.float32).reshape(-1, 4)
+    stride = int(sample_stride)
+    if stride < 1 or s.shape[0] % stride:
+        raise ValueError(f"{s.shape[0]} samples are not a multiple of sample_stride = {stride}")
+    pixels = s.shape[0] // stride
+    ex = None if extra is None else np.ascontiguousarray(extra, np.uint32).reshape(-1)
+    planes = [None if x is None else np.ascontiguousarray(x, np.float32).reshape(-1) for x in (motion, motion_prev, history)]
+    for name, x, size in (("extra", ex, pixels), ("motion", planes[0], 2 * pixels), ("motion_prev", planes[1], 2 * pixels),
+                          ("history", planes[2], 4 * pixels)):
+        if x is not None and x.shape[0] != size:
+            raise ValueError(f"{name} must hold {size} elements, not {x.shape[0]}")
+    out = np.empty((pixels, 4), np.float32)
+    ptr = lambda x: None if x is None else x.ctypes.data
+    _check(_lib().rt_debug_resolve_samples_host(C.byref(uniforms), s.ctypes.data, stride, ptr(ex), ptr(planes[0]),
+                                                ptr(planes[1]), ptr(planes[2]), pixels, out.ctypes.data))
+    return out
 
 
 class RendererQueries:
